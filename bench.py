@@ -5,6 +5,11 @@ process per GPU (torchrun sets RANK/LOCAL_RANK/WORLD_SIZE), rank 0 hosts the con
 plane (apiserver + scheduler + GPU plugin), every rank executes its GPU's pods on
 CU-masked streams with the native MFMA/HBM kernels, placements and telemetry move over
 RCCL.  Prints ONE JSON line on rank 0 (metric/config from BASELINE.json).
+
+A plain run sets up, warms up, times the K steps and prints that line (`ms_per_step` is one
+timed step).  `--dump-outputs DIR` also writes what the last timed step computed (placements,
+each pod's kernel outputs) as DIR/<name>.npy, the same from run to run; `--full` is where
+measurements that need runs of their own go (none today).
 """
 import os
 import sys

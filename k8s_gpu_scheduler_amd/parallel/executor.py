@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 import time
+import zlib
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -47,7 +48,9 @@ class PodRun:
 class _Buffers:
     def __init__(self, w: Workload, device: torch.device):
         self.ops: List[Tuple[Op, tuple]] = []
-        g = torch.Generator(device="cpu").manual_seed(hash(w.name) & 0xFFFF)
+        # (a CRC of the name, not hash(): str hashes change from process to process, and two runs
+        # of the bench must feed the kernels the same operands)
+        g = torch.Generator(device="cpu").manual_seed(zlib.crc32(w.name.encode()) & 0xFFFF)
         for o in w.ops:
             if o.is_gemm:
                 a = ((torch.rand(o.M, o.K, generator=g) * 2 - 1).to(torch.bfloat16)).to(device)

@@ -944,7 +944,72 @@ def build_parser() -> argparse.ArgumentParser:
                          "the same (593/594 vs 594/592 pods/s at 20 steps, 625 vs 618 at 60; "
                          "profiles/archive/r03_window/README.md)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): placements.npy, the step's pods as the scheduler granted them (sorted by "
+                         "workload and SLO), and pod<i>_op<j>.npy, the result kernel j of the pod in row i left "
+                         "in its output buffer (an array "
+                         f"above {DUMP_MAX_ELEMS} elements as a fixed, seeded sample).  Operands and arrivals are "
+                         "seeded, so two runs with the same arguments write the same files")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements (runs beyond the timed steps: baselines, "
+                         "other configurations, comparisons).  A plain run does only what the result line needs; "
+                         "today every other figure in that line is bookkeeping of the timed steps themselves, so "
+                         "--full adds no run of its own yet")
     return ap
+
+
+# --dump-outputs: elements kept per array (1 MiB of float32; a step's 4 pods x 3 kernels stay far
+# below the 64 MB a dump may take); larger arrays are sampled at indices drawn from this seed
+DUMP_MAX_ELEMS = 1 << 18
+DUMP_SEED = 20240
+
+
+def dump_outputs(path: str, arr: np.ndarray, runs: List[Any], ex: Any, placements: bool = True) -> List[str]:
+    """Write the last timed step's results under `path` (see --dump-outputs); returns the files.
+
+    `arr` is the step's placement array, `runs` this rank's pods of the step, `ex` its executor.
+    Pods are numbered in a canonical order (by workload id, SLO, units, iterations, masked): the
+    array's own row order is the scheduling queue's, and that queue, like the GPU, CU slot and
+    kernel policy columns, follows the measured telemetry of earlier steps, which differs between
+    two runs of one build.  placements.npy (`placements`: rank 0 writes it) keeps the columns a
+    run reproduces -- units, workload id, iterations, SLO (milli-iterations/s), masked -- one
+    row per pod.  The pods' buffers are read after the device has drained: each kernel's output
+    is a function of the workload's seeded operands alone."""
+    os.makedirs(path, exist_ok=True)
+    written = []
+
+    def save(name: str, a: np.ndarray) -> None:
+        f = os.path.join(path, name + ".npy")
+        np.save(f, np.ascontiguousarray(a, dtype=np.float32))
+        written.append(f)
+
+    arr = np.asarray(arr)
+    order = sorted(range(len(arr)), key=lambda i: tuple(int(arr[i][c]) for c in (3, 5, 2, 4, 6)))
+    number = {i: k for k, i in enumerate(order)}
+    if placements:
+        save("placements", arr[order][:, 2:7])
+    bufs_of = getattr(ex, "buffers", None)
+    if bufs_of is not None:
+        for r in runs:
+            k = number[r.pod_id]
+            bufs = bufs_of(W.get(r.workload), r.first_unit, r.n_units)
+            for j, (o, t) in enumerate(bufs.ops):
+                out = (t[3] if o.is_gemm else t[0]).reshape(-1)
+                idx = dump_sample(out.numel(), k, j)
+                if idx is not None:
+                    out = out[idx.to(out.device)]
+                save(f"pod{k}_op{j}", out.float().cpu().numpy())
+    return written
+
+
+def dump_sample(numel: int, pod: int, op: int) -> Optional[torch.Tensor]:
+    """The flat indices pod<pod>_op<op>.npy keeps of an output of `numel` elements (ascending;
+    None: the whole array)."""
+    if numel <= DUMP_MAX_ELEMS:
+        return None
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED + 1000 * pod + op)
+    return torch.randint(numel, (DUMP_MAX_ELEMS,), generator=g).sort().values
 
 
 def gpu_executor(a: Any, dev_idx: int = 0) -> Any:
@@ -1196,6 +1261,7 @@ def main(argv: Optional[List[str]] = None) -> Dict[str, Any]:
                 host["launch"] += t2 - t1
                 host["schedule"] += time.perf_counter() - t2
             pending.append((runs, arr))
+            state["last"] = (runs, arr)
             if placements is not None and rank == 0:
                 placements.append({"timed": bool(timed), "arr": arr.tolist()})
             while len(pending) > a.lookahead:
@@ -1252,6 +1318,8 @@ def main(argv: Optional[List[str]] = None) -> Dict[str, Any]:
         with open(marker_path, "w") as f:
             json.dump({"pods": timed_pods, "gemm_share": bool(ex.gemm_share)}, f)
     wall1 = time.time()
+    if a.dump_outputs and a.steps > 0:
+        dump_outputs(a.dump_outputs, state["last"][1], state["last"][0], ex, placements=rank == 0)
     if use_gpu and trace is not None:
         fin = torch.cuda.Event(enable_timing=True)
         fin.record(side)

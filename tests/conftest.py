@@ -7,8 +7,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-REF_DATA = "/root/reference/pkg/recommender/recommender"
-REF_PROM = "/root/reference/pkg/prom/test_data"
+# the reference's data files the parity tests read (training matrices, Prometheus responses,
+# its scheduler manifest), stored with the tests
+GOLDEN_REF = os.path.join(ROOT, "tests", "golden", "reference")
+REF_DATA = GOLDEN_REF
+REF_PROM = GOLDEN_REF
 
 
 def pytest_configure(config):
@@ -36,12 +39,10 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def ref_data():
-    """The reference's shipped training matrices (read in place, never copied); parity
-    tests skip when the reference checkout is not mounted."""
+    """The reference's shipped training matrices (tests/golden/reference)."""
     conf = os.path.join(REF_DATA, "configurations_train.ods")
     intf = os.path.join(REF_DATA, "interference_train.ods")
-    if not (os.path.isfile(conf) and os.path.isfile(intf)):
-        pytest.skip("reference data not mounted")
+    assert os.path.isfile(conf) and os.path.isfile(intf), "tests/golden/reference is incomplete"
     return conf, intf
 
 

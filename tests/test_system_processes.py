@@ -5,9 +5,11 @@ election on a Lease) -- pods created over REST get bound with their device assig
 the scheduler's /metrics counts them."""
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 import urllib.request
 
@@ -28,6 +30,17 @@ def _free_port() -> int:
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def _socket_dir(tmp_path, longest_name):
+    """A directory for Unix sockets: tmp_path when `longest_name` in it fits sockaddr_un's
+    107 bytes (pytest's base directory can be deep), else a fresh short one."""
+    if len(os.path.join(str(tmp_path), longest_name).encode()) <= 107:
+        return str(tmp_path), False
+    for base in (tempfile.gettempdir(), "/tmp", "/dev/shm"):
+        if os.path.isdir(base) and os.access(base, os.W_OK) and len(base) + len(longest_name) + 16 <= 107:
+            return tempfile.mkdtemp(prefix="dp-", dir=base), True
+    raise RuntimeError(f"no writable directory short enough for a Unix socket named {longest_name}")
 
 
 def _spawn(args, **kw):
@@ -121,7 +134,8 @@ def test_agent_serves_device_plugin_to_kubelet_as_process(tmp_path):
         "Register": grpc.unary_unary_rpc_method_handler(
             lambda req, ctx: (regs.append(req.resource_name), dp.Empty())[1],
             request_deserializer=dp.RegisterRequest.FromString, response_serializer=dp.Empty.SerializeToString)}),))
-    kubelet.add_insecure_port(f"unix://{tmp_path}/kubelet.sock")
+    sock_dir, own_dir = _socket_dir(tmp_path, max([dp.socket_name(r) for r in dp.RESOURCES] + ["kubelet.sock"], key=len))
+    kubelet.add_insecure_port(f"unix://{sock_dir}/kubelet.sock")
     kubelet.start()
     try:
         api_port = _free_port()
@@ -132,7 +146,7 @@ def test_agent_serves_device_plugin_to_kubelet_as_process(tmp_path):
         node = O.name(client.list("nodes")[0][0])
         ag = _spawn(["agent", "--fake-apiserver", url, "--redis", redis.addr, "--node", node, "--synthetic", "8",
                      "--no-discovery", "--metrics-port", "0", "--poll", "0.5",
-                     "--device-plugin", "--device-plugin-dir", str(tmp_path)])
+                     "--device-plugin", "--device-plugin-dir", sock_dir])
         procs.append(ag)
         assert _wait(lambda: len(regs) >= 3, 60), regs
         assert sorted(regs) == sorted(dp.RESOURCES)
@@ -146,7 +160,7 @@ def test_agent_serves_device_plugin_to_kubelet_as_process(tmp_path):
                 p.terminate()
             logs = "\n".join(f"--- {p.args[3:5]}\n" + (p.communicate(timeout=10)[0] or "")[-3000:] for p in procs)
             raise AssertionError("pod not bound; process output:\n" + logs)
-        ch = grpc.insecure_channel(f"unix://{tmp_path}/{dp.socket_name(C.RESOURCE_GPU_CU)}")
+        ch = grpc.insecure_channel(f"unix://{sock_dir}/{dp.socket_name(C.RESOURCE_GPU_CU)}")
         alloc = ch.unary_unary(f"/{dp.PLUGIN_SERVICE}/Allocate", request_serializer=dp.AllocateRequest.SerializeToString,
                                response_deserializer=dp.AllocateResponse.FromString)
         req = dp.AllocateRequest()
@@ -166,6 +180,8 @@ def test_agent_serves_device_plugin_to_kubelet_as_process(tmp_path):
                 p.kill()
         kubelet.stop(0)
         redis.stop()
+        if own_dir:
+            shutil.rmtree(sock_dir, ignore_errors=True)
 
 
 @pytest.mark.timeout(240)

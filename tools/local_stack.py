@@ -26,7 +26,7 @@ from k8s_gpu_scheduler_amd.api import objects as O  # noqa: E402
 from k8s_gpu_scheduler_amd.kube.rest import RestClient, RestConfig  # noqa: E402
 from k8s_gpu_scheduler_amd.store.fake_redis import FakeRedisEngine, FakeRedisServer  # noqa: E402
 
-REF_DATA = "/root/reference/pkg/recommender/recommender"
+REF_DATA = os.path.join(ROOT, "tests", "golden", "reference")     # the reference's training matrices
 
 
 def free_port() -> int:

@@ -19,7 +19,7 @@ from k8s_gpu_scheduler_amd.framework.scheduler import Scheduler  # noqa: E402
 from k8s_gpu_scheduler_amd.kube.client import FakeCluster  # noqa: E402
 from k8s_gpu_scheduler_amd.plugins import full_registry  # noqa: E402
 
-REF = "/root/reference/pkg/recommender/recommender"
+REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference")
 PARITY_PROFILE = """
 apiVersion: kubescheduler.config.k8s.io/v1beta1
 kind: KubeSchedulerConfiguration
