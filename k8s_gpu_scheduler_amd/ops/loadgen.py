@@ -3,7 +3,25 @@
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM.  Shapes are validated on the host before launch (the kernels have no bounds checks
 by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
-path here (tests compare against torch fp32 references instead).
+path here (tests compare against torch fp32 / fp64 references instead).
+
+Operands may be views into larger allocations (row slices, column slices, padded rows).  The
+host checks enforce, and tests/test_gpu_kernels_exact.py relies on:
+
+  * A, Bt: K-contiguous rows, the first element 16-byte aligned, the leading dimension (row
+    stride in elements) >= K and a multiple of 8 for bf16, of 16 for fp8 -- every row then
+    starts on a 16-byte boundary, which the 16-byte global->LDS loads need;
+  * C: N-contiguous rows, ldc >= N, rows 8-byte aligned (ldc a multiple of 4, the first
+    element 8-byte aligned).  With 16-byte aligned rows (ldc a multiple of 8, the first element
+    16-byte aligned) the bf16 kernels take the wide 16-byte-store epilogue, otherwise the 8-byte
+    one.  The 4-wave kernels (tiles 14-16) only have the wide epilogue: forced (set_gemm_tile) on
+    a C that is not 16-byte aligned they raise, chosen by a policy they give way to the 8-phase /
+    128 x 128 kernels;
+  * bias: a contiguous fp32 vector of length N, 16-byte aligned;
+  * triad: three contiguous fp32 arrays of equal length, a multiple of 4, each 16-byte aligned.
+
+Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
+written.
 """
 from __future__ import annotations
 
