@@ -17,6 +17,10 @@ selects a different layer shape (onnx: 2048-wide, tensorflow: 1536/2560-wide).  
 *iteration* ("query batch") runs the op list once; a pod's throughput is iterations/s,
 its SLO a minimum iterations/s -- the same semantics as the reference's SLO env
 (SURVEY.md §2.7.1).
+
+A third kernel character exists outside the catalog (EXTRA): "gather", the bf16 embedding-bag
+(ops.loadgen.embedding_bag) -- memory-bound like the triad, but random table rows instead of a
+stream, no MFMA work, and a rate that depends on where the rows sit (L2 > Infinity Cache > HBM).
 """
 from __future__ import annotations
 
@@ -26,12 +30,13 @@ from typing import Dict, List, Optional, Tuple
 
 @dataclass(frozen=True)
 class Op:
-    kind: str              # "gemm" (bf16) | "gemm8" (fp8 e4m3, bf16 out) | "triad"
-    M: int = 0
-    N: int = 0
-    K: int = 0
+    kind: str              # "gemm" (bf16) | "gemm8" (fp8 e4m3, bf16 out) | "triad" | "gather" (bf16 embedding bag)
+    M: int = 0             # gather: bags
+    N: int = 0             # gather: D, the row length
+    K: int = 0             # gather: pooling factor (rows per bag)
     relu: bool = True
     n_floats: int = 0      # triad
+    rows: int = 0          # gather: rows of the table
 
     @property
     def is_gemm(self) -> bool:
@@ -39,6 +44,8 @@ class Op:
 
     @property
     def flops(self) -> float:
+        if self.kind == "gather":
+            return 1.0 * self.M * self.K * self.N                 # one add per gathered element
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -47,6 +54,8 @@ class Op:
             return 2.0 * (self.M * self.K + self.N * self.K + self.M * self.N)
         if self.kind == "gemm8":
             return 1.0 * (self.M * self.K + self.N * self.K) + 2.0 * self.M * self.N
+        if self.kind == "gather":                                 # rows read, indices, offsets, output
+            return 2.0 * self.M * self.K * self.N + 4.0 * self.M * self.K + 4.0 * (self.M + 1) + 2.0 * self.M * self.N
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -113,10 +122,18 @@ INDEX: Dict[str, int] = {n: i for i, n in enumerate(NAMES)}
 #   fp8_llm_2048     three fp8 GEMMs 2048 x 4096 x 4096 (LLM-projection-like, MFMA-bound on
 #                    the block-scaled fp8 MFMA the catalog never uses)
 #   triad_only_2048  three HBM stream passes, no GEMM at all
+#   dlrm_2048        DLRM-like: 26 embedding lookups per sample (2048 x 26 bags of 32 random
+#                    256-byte rows from a 1 GiB table -- four times the Infinity Cache, so the rows
+#                    come from HBM), then two bf16 GEMMs (the top MLP over the 26 x 128 pooled
+#                    features).  The gather is a third kernel character (indexed rows); no co-run
+#                    groups are measured with it yet
 EXTRA: Dict[str, Workload] = {
     "fp8_llm_2048": Workload("fp8_llm_2048", "llm_fp8", "hip", 2048, (Op("gemm8", 2048, 4096, 4096),) * 3, 1.0),
     "triad_only_2048": Workload("triad_only_2048", "stream", "hip", 2048,
                                 (Op("triad", n_floats=2048 * 16384),) * 3, 1.0),
+    "dlrm_2048": Workload("dlrm_2048", "dlrm", "hip", 2048,
+                          (Op("gather", 2048 * 26, 128, 32, rows=4 * 1024 * 1024),
+                           Op("gemm", 2048, 1024, 3328), Op("gemm", 2048, 1024, 1024)), 1.25),
 }
 
 
@@ -194,10 +211,22 @@ def default_gemm_workgroups(M: int, N: int, K: int, cu_budget: int = 0, fp8: boo
     return (M // bm) * (N // bn)
 
 
+GATHER_BAGS_PER_WORKGROUP = 4      # one wave per bag, 256-thread workgroups (native/hip/gather.hip)
+
+
+def default_gather_workgroups(B: int, blocks: int = 0) -> int:
+    """Workgroups the native embedding-bag launch gets for B bags (blocks > 0 caps the grid) -- a
+    pure-Python copy of embedding_bag_workgroups (native/hip/gather.hip), pinned against it in
+    tests/test_gather_cpu.py."""
+    need = -(-B // GATHER_BAGS_PER_WORKGROUP)
+    return blocks if 0 < blocks < need else need
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
-    launches them for `cu_budget` under the default policy (default_gemm_workgroups), the
+    launches them for `cu_budget` under the default policy (default_gemm_workgroups), gather
+    workgroups as default_gather_workgroups counts them, the
     stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
@@ -206,6 +235,8 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
         dt = roofline_seconds(Workload(w.name, w.family, w.framework, w.batch, (o,), 0.0), 1.0)
         if o.is_gemm:
             fo = min(1.0, default_gemm_workgroups(o.M, o.N, o.K, cu_budget, o.kind == "gemm8") / CUS)
+        elif o.kind == "gather":
+            fo = min(1.0, default_gather_workgroups(o.M) / CUS)
         else:
             fo = 1.0
         t += dt

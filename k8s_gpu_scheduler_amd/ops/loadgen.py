@@ -1,12 +1,14 @@
-"""Torch-facing wrappers for the HIP load kernels (native/hip/loadgen.hip).
+"""Torch-facing wrappers for the HIP load kernels (native/hip/loadgen.hip, native/hip/gather.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
-e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM.  Shapes are validated on the host before launch (the kernels have no bounds checks
-by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
+e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
+`embedding_bag(table, idx, offsets)` gathers indexed table rows and sums them per bag (random-row
+HBM / cache traffic, no MFMA).  Shapes are validated on the host before launch (the kernels
+have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
 Operands may be views into larger allocations (row slices, column slices, padded rows).  The
-host checks enforce, and tests/test_gpu_kernels_exact.py relies on:
+host checks enforce, and tests/test_gpu_kernels_exact.py and test_gpu_gather_exact.py rely on:
 
   * A, Bt: K-contiguous rows, the first element 16-byte aligned, the leading dimension (row
     stride in elements) >= K and a multiple of 8 for bf16, of 16 for fp8 -- every row then
@@ -18,10 +20,18 @@ host checks enforce, and tests/test_gpu_kernels_exact.py relies on:
     a C that is not 16-byte aligned they raise, chosen by a policy they give way to the 8-phase /
     128 x 128 kernels;
   * bias: a contiguous fp32 vector of length N, 16-byte aligned;
-  * triad: three contiguous fp32 arrays of equal length, a multiple of 4, each 16-byte aligned.
+  * triad: three contiguous fp32 arrays of equal length, a multiple of 4, each 16-byte aligned;
+  * embedding_bag: table bf16 R x D and out bf16 B x D with D-contiguous rows, D a power of two
+    in [64, 2048], row strides >= D and multiples of 8, the first elements 16-byte aligned (every
+    row then is, which the 16-byte row loads and stores need); idx int32 (1-D of length L with
+    offsets, or 2-D [B, P] without: fixed pooling) and offsets int32 of length B + 1 (CSR bags:
+    non-decreasing, offsets[0] >= 0, offsets[B] <= L), both contiguous, 4-byte aligned.  The
+    kernel trusts the indices: check_indices=True verifies 0 <= idx < R and the offsets on the
+    device first (one sync); a caller that passes False guarantees them itself.
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
-written.
+written; the gather reads only the D elements of the rows the bags name (and the idx entries
+[offsets[0], offsets[B]) and the offsets) and writes only the B x D window.
 """
 from __future__ import annotations
 
@@ -151,6 +161,81 @@ def triad(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, s: float = 1.5, blo
         _native.hip().stream_triad(a.data_ptr(), b.data_ptr(), c.data_ptr(), float(s), n, int(blocks),
                                    _stream_ptr(stream, a.device))
     return a
+
+
+GATHER_D_MIN, GATHER_D_MAX = 64, 2048
+
+
+def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, blocks: int = 0, stream: Optional[torch.cuda.Stream] = None,
+                  check_indices: bool = True) -> torch.Tensor:
+    """out[b, :] = bf16(sum of table[idx[j], :] over j in [offsets[b], offsets[b+1])) -- bf16 rows,
+    fp32 accumulate, one rounding; an empty bag gives a row of +0.0.  idx 2-D [B, P] (no offsets):
+    bag b is row b.  blocks > 0 caps the grid (the workgroups walk the bags grid-stride).
+    check_indices=False skips the device-side range check (and its sync): for callers whose
+    indices are in range by construction, and under graph capture."""
+    _check_devices("embedding_bag", table, idx, offsets, out)
+    if table.dtype != torch.bfloat16:
+        raise TypeError("embedding_bag expects a bf16 table")
+    if idx.dtype != torch.int32 or (offsets is not None and offsets.dtype != torch.int32):
+        raise TypeError("embedding_bag expects int32 indices and offsets")
+    if table.dim() != 2 or table.stride(1) != 1:
+        raise ValueError("embedding_bag expects a row-major (D-contiguous) 2-D table")
+    R, D = table.shape
+    if D < GATHER_D_MIN or D > GATHER_D_MAX or D & (D - 1):
+        raise ValueError(f"embedding_bag: D = {D} must be a power of two in [{GATHER_D_MIN}, {GATHER_D_MAX}]")
+    if R > 1 and (table.stride(0) < D or table.stride(0) % 8):
+        raise ValueError(f"embedding_bag: table row stride {table.stride(0)} must be >= D and a multiple of 8")
+    if table.data_ptr() % 16:
+        raise ValueError("embedding_bag: table must be 16-byte aligned")
+    if idx.dim() == 2:
+        if offsets is not None:
+            raise ValueError("embedding_bag: a 2-D idx is fixed pooling and takes no offsets")
+        if not idx.is_contiguous():
+            raise ValueError("embedding_bag expects contiguous indices")
+        B, P = idx.shape
+        if B * P >= 2 ** 31:
+            raise ValueError("embedding_bag: more than 2^31 - 1 indices")
+        offsets = torch.arange(B + 1, dtype=torch.int32, device=idx.device) * P
+        idx = idx.reshape(-1)
+    elif idx.dim() == 1:
+        if offsets is None:
+            raise ValueError("embedding_bag: a 1-D idx needs offsets")
+        if offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("embedding_bag: offsets must be 1-D of length B + 1")
+        if not idx.is_contiguous() or not offsets.is_contiguous():
+            raise ValueError("embedding_bag expects contiguous indices and offsets")
+        B = offsets.numel() - 1
+    else:
+        raise ValueError(f"embedding_bag: idx must be 1-D or 2-D (got {idx.dim()}-D)")
+    L = idx.numel()
+    if L >= 2 ** 31 or B >= 2 ** 31:
+        raise ValueError("embedding_bag: more than 2^31 - 1 indices or bags")
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.bfloat16, device=table.device)
+    if out.dim() != 2 or out.shape != (B, D) or out.dtype != torch.bfloat16 or out.stride(1) != 1:
+        raise ValueError("bad output tensor")
+    if B > 1 and (out.stride(0) < D or out.stride(0) % 8):
+        raise ValueError(f"embedding_bag: output row stride {out.stride(0)} must be >= D and a multiple of 8")
+    if out.data_ptr() % 16:
+        raise ValueError("embedding_bag: out must be 16-byte aligned")
+    ld_table = table.stride(0) if R > 1 else D
+    ld_out = out.stride(0) if B > 1 else D
+    h = _native.hip()
+    with torch.cuda.device(table.device):
+        sp = _stream_ptr(stream, table.device)
+        if check_indices:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(table.device)):
+                bad = torch.stack([((idx < 0) | (idx >= R)).any(), (offsets[1:] < offsets[:-1]).any(),
+                                   offsets[0] < 0, offsets[-1] > L]).tolist()          # the one sync
+            if bad[0]:
+                raise ValueError(f"embedding_bag: an index is outside [0, {R})")
+            if bad[1] or bad[2] or bad[3]:
+                raise ValueError(f"embedding_bag: offsets must be non-decreasing within [0, {L}]")
+        if B:
+            h.embedding_bag_bf16(table.data_ptr(), idx.data_ptr(), offsets.data_ptr(), out.data_ptr(), B, D,
+                                 ld_table, ld_out, int(blocks), sp)
+    return out
 
 
 def gemm_flops(M: int, N: int, K: int) -> float:

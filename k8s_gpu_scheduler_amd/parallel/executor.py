@@ -45,6 +45,9 @@ class PodRun:
         return self.iters / (self.ms / 1e3) if self.ms > 0 else 0.0
 
 
+GATHER_BLOCK_ROWS = 4096          # rows of the CPU-generated block a gather table repeats
+
+
 class _Buffers:
     def __init__(self, w: Workload, device: torch.device):
         self.ops: List[Tuple[Op, tuple]] = []
@@ -60,11 +63,28 @@ class _Buffers:
                 bias = torch.zeros(o.N, dtype=torch.float32, device=device)
                 c = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
                 self.ops.append((o, (a, bt, bias, c)))
-            else:
+            elif o.kind == "gather":
+                # M bags of K rows of N elements out of a table of o.rows rows.  The table is one
+                # small CPU-generated block repeated on the device (no GiB on the host); its values
+                # are k / 128, |k| <= 127: every fp32 partial sum of a bag is exact, so the output
+                # does not depend on the kernel's summation order
+                n = min(o.rows, GATHER_BLOCK_ROWS)
+                blk = ((torch.randint(-127, 128, (n, o.N), generator=g).float() / 128).to(torch.bfloat16)).to(device)
+                table = torch.empty(o.rows, o.N, dtype=torch.bfloat16, device=device)
+                full = o.rows // n * n
+                table[:full].view(-1, n, o.N).copy_(blk)
+                table[full:].copy_(blk[:o.rows - full])
+                idx = torch.randint(o.rows, (o.M * o.K,), generator=g, dtype=torch.int32).to(device)
+                offsets = (torch.arange(o.M + 1, dtype=torch.int32) * o.K).to(device)
+                out = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
+                self.ops.append((o, (out, table, idx, offsets)))
+            elif o.kind == "triad":
                 x = torch.ones(o.n_floats, dtype=torch.float32, device=device)
                 y = torch.ones(o.n_floats, dtype=torch.float32, device=device)
                 z = torch.ones(o.n_floats, dtype=torch.float32, device=device)
                 self.ops.append((o, (x, y, z)))
+            else:
+                raise ValueError(f"workload {w.name}: unknown op kind {o.kind!r}")
 
 
 def enqueue_ops(bufs: _Buffers, iters: int, st, budget: int, blocks: int = 0) -> None:
@@ -78,9 +98,15 @@ def enqueue_ops(bufs: _Buffers, iters: int, st, budget: int, blocks: int = 0) ->
             elif o.kind == "gemm8":
                 a, bt, bias, c = t
                 loadgen.gemm_fp8(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
-            else:
+            elif o.kind == "gather":
+                # the indices were generated in range: no check, no sync (this runs under capture)
+                out, table, idx, offsets = t
+                loadgen.embedding_bag(table, idx, offsets, out=out, stream=st, check_indices=False)
+            elif o.kind == "triad":
                 x, y, z = t
                 loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
+            else:
+                raise ValueError(f"unknown op kind {o.kind!r}")
 
 
 def lpt_balance(runs: List[PodRun], slot_work: Dict[Tuple[int, int], float], work=None) -> None:

@@ -30,6 +30,12 @@ void set_split_k(int s);
 void gemm_fp8_nt(uintptr_t a, uintptr_t bt, uintptr_t c, uintptr_t bias, int M, int N, int K, int lda, int ldb,
                  int ldc, bool relu, uintptr_t stream, int cu_budget);
 void stream_triad(uintptr_t a, uintptr_t b, uintptr_t c, float s, size_t n_floats, int blocks, uintptr_t stream);
+// out[b, :] = bf16(sum of table[idx[j], :] over j in [offsets[b], offsets[b+1])) -- native/hip/gather.hip;
+// strides in elements, blocks > 0 caps the grid (the workgroups then walk the bags grid-stride)
+void embedding_bag_bf16(uintptr_t table, uintptr_t idx, uintptr_t offsets, uintptr_t out, int B, int D,
+                        int64_t ld_table, int64_t ld_out, int blocks, uintptr_t stream);
+// workgroups of that launch
+int embedding_bag_workgroups(int B, int blocks);
 void set_triad_variant(int v);
 void set_gemm_tile(int t);
 void set_w4_probe(int mask);

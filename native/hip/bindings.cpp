@@ -61,6 +61,10 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("stream"), py::arg("cu_budget") = 0, py::call_guard<py::gil_scoped_release>());
   m.def("stream_triad", &gs::stream_triad, py::arg("a"), py::arg("b"), py::arg("c"), py::arg("s"),
         py::arg("n_floats"), py::arg("blocks"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("embedding_bag_bf16", &gs::embedding_bag_bf16, py::arg("table"), py::arg("idx"), py::arg("offsets"),
+        py::arg("out"), py::arg("B"), py::arg("D"), py::arg("ld_table"), py::arg("ld_out"), py::arg("blocks"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("embedding_bag_workgroups", &gs::embedding_bag_workgroups, py::arg("B"), py::arg("blocks") = 0);
   m.def("set_triad_variant", &gs::set_triad_variant, py::arg("variant"));
   m.def("set_gemm_tile", &gs::set_gemm_tile, py::arg("tile"));
   m.def("set_w4_probe", &gs::set_w4_probe, py::arg("mask"));
