@@ -26,12 +26,33 @@ host checks enforce, and tests/test_gpu_kernels_exact.py and test_gpu_gather_exa
     row then is, which the 16-byte row loads and stores need); idx int32 (1-D of length L with
     offsets, or 2-D [B, P] without: fixed pooling) and offsets int32 of length B + 1 (CSR bags:
     non-decreasing, offsets[0] >= 0, offsets[B] <= L), both contiguous, 4-byte aligned.  The
-    kernel trusts the indices: check_indices=True verifies 0 <= idx < R and the offsets on the
-    device first (one sync); a caller that passes False guarantees them itself.
+    kernel trusts the indices: check_indices=True verifies the offsets and 0 <= idx[j] < R for the
+    j in [offsets[0], offsets[B]) -- the entries the bags name; the others are never read as
+    indices -- on the device first (one sync); a caller that passes False guarantees them itself.
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
 [offsets[0], offsets[B]) and the offsets) and writes only the B x D window.
+
+Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
+of the conversion and float64 sums):
+
+  * every bf16 output is the round-to-nearest-even encoding of its fp32 value over the whole fp32
+    range: ties go to the even neighbour, a rounding may carry into the exponent, values past the
+    largest finite bf16 (from 0x7F7F8000 on) become +-Inf;
+  * subnormals are kept, in the fp32 arithmetic (bias add, gather and triad sums, MFMA
+    accumulators) and in the conversion: an fp32 subnormal rounds to a bf16 subnormal or to +-0,
+    nothing is flushed;
+  * a NaN in gives a NaN out in every cell that depends on it and in no other (Inf * 0 and
+    Inf - Inf are NaN too: no zero is skipped); which NaN -- sign and payload -- is unspecified, also
+    for NaNs whose payload lies only in the 16 bits the conversion drops.  An fp32 accumulator that
+    overflows gives +-Inf;
+  * ReLU is `v > 0 ? v : 0` in every epilogue: NaN and every negative value, -0.0 and -Inf
+    included, give +0.0 -- unlike torch.relu, which passes NaN on;
+  * without ReLU, -0.0 survives only where nothing is added to it: the GEMM epilogues compute
+    acc + bias with acc = +0.0 for all-zero operands, so a bias of -0.0 gives +0.0; the gather
+    starts every bag at +0.0, so an empty bag and a bag of a single -0.0 row give +0.0 (bit
+    pattern 0x0000); the triad's -0.0 + s * -0.0 is -0.0 for s > 0.
 """
 from __future__ import annotations
 
@@ -226,7 +247,9 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torc
         sp = _stream_ptr(stream, table.device)
         if check_indices:
             with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(table.device)):
-                bad = torch.stack([((idx < 0) | (idx >= R)).any(), (offsets[1:] < offsets[:-1]).any(),
+                pos = torch.arange(L, dtype=torch.int32, device=idx.device)
+                named = (pos >= offsets[0]) & (pos < offsets[-1])      # only these are read as indices
+                bad = torch.stack([(((idx < 0) | (idx >= R)) & named).any(), (offsets[1:] < offsets[:-1]).any(),
                                    offsets[0] < 0, offsets[-1] > L]).tolist()          # the one sync
             if bad[0]:
                 raise ValueError(f"embedding_bag: an index is outside [0, {R})")

@@ -4,9 +4,9 @@ MI355X), in the style of test_gpu_kernels_exact.py, whose guard helpers and sent
 Two value regimes make the fp32 bag sums exact, hence independent of the summation order; the
 comparison with a float64 reference (index_select + a per-bag sum) is `torch.equal`:
 
-  rep   table integers in [-4, 4], bags of at most 64 rows: |ref| <= 256 (asserted on the
-        reference alone), so bf16 holds every expected value exactly.
-  rnd   table values k / 8 with |k| <= 64 (each one a bf16), bags of at most 64 rows: sums are
+  rep   table integers in [-4, 4], bags of at most 64 rows (129 in the long-bag case): |ref| <= 256
+        (asserted on the reference alone), so bf16 holds every expected value exactly.
+  rnd   table values k / 8 with |k| <= 64 (each one a bf16), bags of at most 64 (129) rows: sums are
         multiples of 1/8 below 512, exact in fp32; most outputs need the bf16 rounding and many
         are ties, which pins round-to-nearest-even (a tie is asserted on the reference alone).
 
@@ -93,8 +93,8 @@ def guarded_table(values, idx):
 
 
 class Case:
-    def __init__(self, values, idx, offsets, regime, need_tie=False):
-        assert int(offsets.diff().max()) <= MAX_BAG
+    def __init__(self, values, idx, offsets, regime, need_tie=False, max_bag=MAX_BAG):
+        assert int(offsets.diff().max()) <= max_bag
         self.B, self.D, self.R, self.regime = offsets.numel() - 1, values.shape[1], values.shape[0], regime
         self.exp = expected(reference(values, idx, offsets), regime, need_tie).cuda()
         self.table = guarded_table(values, idx)
@@ -143,9 +143,9 @@ def boundary_case(D, regime):
 
 
 @pytest.mark.parametrize("regime", REGIMES)
-@pytest.mark.parametrize("D", [64, 128, 512, 1024, 2048])
+@pytest.mark.parametrize("D", [64, 128, 256, 512, 1024, 2048])
 def test_bag_length_boundaries(hip, D, regime):
-    """Remainders of the 4 steps in flight and (D = 64) of the 8 rows per wave-instruction, empty
+    """Remainders of the 4 steps in flight and (D <= 256) of the 8 / 4 / 2 rows per wave-instruction, empty
     bags (exactly +0.0, not the sentinel), rows 0 and R - 1, repeated and shared rows."""
     from k8s_gpu_scheduler_amd.ops import loadgen
     c = boundary_case(D, regime)
@@ -155,6 +155,56 @@ def test_bag_length_boundaries(hip, D, regime):
     c.check((D, regime))
     bits = c.out.view(torch.int16)
     assert not bits[0].any() and not bits[12].any()                 # +0.0: bit pattern 0
+
+
+LONG_LENGTHS = [31, 32, 33, 65, 127, 128, 129]
+LONG_MAX_BAG = 129
+FRONT = 5                  # idx entries in front of offsets[0] in the offset-start case
+
+
+@functools.lru_cache(maxsize=None)
+def long_bag_case(D, regime):
+    g = torch.Generator().manual_seed(D * 11 + (3 if regime == "rnd" else 2))
+    offsets = torch.tensor([0] + LONG_LENGTHS, dtype=torch.int32).cumsum(0).to(torch.int32)
+    idx = torch.randint(R1, (int(offsets[-1]),), generator=g, dtype=torch.int32)
+    idx[-1] = R1 - 1                            # the last row closes the longest bag
+    return Case(table_values(R1, D, regime, g), idx, offsets, regime, need_tie=regime == "rnd", max_bag=LONG_MAX_BAG)
+
+
+@pytest.mark.parametrize("regime", REGIMES)
+@pytest.mark.parametrize("D", [64, 128, 256, 512, 1024, 2048])
+def test_long_bags(hip, D, regime):
+    """Bags of 31 .. 129 rows: more than two full trips of 4 steps at every D (at D = 64 a trip is
+    32 rows, at D >= 512 four), each with a ragged tail of every kind around the trip lengths."""
+    from k8s_gpu_scheduler_amd.ops import loadgen
+    c = long_bag_case(D, regime)
+    assert c.B == 7 and max(LONG_LENGTHS) > 2 * 4 * max(1, 512 // D)
+    c.resentinel()
+    loadgen.embedding_bag(c.table, c.idx, c.offsets, out=c.out)
+    c.check((D, regime, "long"))
+
+
+@pytest.mark.parametrize("regime", REGIMES)
+@pytest.mark.parametrize("D", [64, 256, 1024])
+def test_offsets_start_past_zero(hip, D, regime):
+    """offsets[0] = 5: the five idx entries in front of the first bag hold SENT32 (no valid row);
+    neither the kernel nor the index check may read them as indices."""
+    from k8s_gpu_scheduler_amd.ops import loadgen
+    c = boundary_case(D, regime)
+    front = torch.full((FRONT,), SENT32, dtype=torch.int32)
+    _, idx = guarded_ints(torch.cat([front, c.idx.cpu()]))
+    _, offsets = guarded_ints(c.offsets.cpu() + FRONT)
+    assert int(offsets[0]) == FRONT and int(offsets[-1]) == idx.numel() and int(idx[FRONT - 1]) == SENT32
+    for check in (True, False):
+        c.resentinel()
+        loadgen.embedding_bag(c.table, idx, offsets, out=c.out, check_indices=check)
+        c.check((D, regime, "offsets[0] = 5", check))
+    bad = idx.clone()
+    bad[FRONT] = SENT32                         # the first entry that is an index
+    c.resentinel()
+    with pytest.raises(ValueError):
+        loadgen.embedding_bag(c.table, bad, offsets, out=c.out)
+    assert c.untouched()
 
 
 # ------------------------------------------------------------------------------------------------

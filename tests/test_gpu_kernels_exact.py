@@ -121,7 +121,7 @@ def expected(ref, bias, relu, use_bias, regime):
         cap = r.abs().max().item()
         assert cap <= REP_CAP, f"representable regime: max|ref| = {cap} > {REP_CAP}; lower the density"
     if relu:
-        r = r.clamp_min(0.0)
+        r = r.clamp_min(0.0)       # valid only because no NaN reaches it: the kernels' ReLU makes NaN +0.0, this keeps it
     return r.float() if regime == "rep" else r.float().to(torch.bfloat16)
 
 
