@@ -21,6 +21,9 @@ its SLO a minimum iterations/s -- the same semantics as the reference's SLO env
 A third kernel character exists outside the catalog (EXTRA): "gather", the bf16 embedding-bag
 (ops.loadgen.embedding_bag) -- memory-bound like the triad, but random table rows instead of a
 stream, no MFMA work, and a rate that depends on where the rows sit (L2 > Infinity Cache > HBM).
+A fourth is "attn", decode attention over a paged KV cache (ops.loadgen.paged_decode_attention):
+HBM-bound too, but its traffic is 8 KiB cache slabs named by a block table, its two products run on
+the matrix cores, and it has a softmax (transcendentals, cross-lane reductions) in the loop.
 """
 from __future__ import annotations
 
@@ -28,15 +31,20 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 
+ATTN_HEAD_DIM = 128               # the decode-attention kernel's head dim ...
+ATTN_BLOCK_TOKENS = 32            # ... and KV-cache block size (native/hip/decode_attn.hip)
+
+
 @dataclass(frozen=True)
 class Op:
     kind: str              # "gemm" (bf16) | "gemm8" (fp8 e4m3, bf16 out) | "triad" | "gather" (bf16 embedding bag)
-    M: int = 0             # gather: bags
-    N: int = 0             # gather: D, the row length
-    K: int = 0             # gather: pooling factor (rows per bag)
+    #                        | "attn" (bf16 paged-KV decode attention, head dim 128, blocks of 32 tokens)
+    M: int = 0             # gather: bags; attn: sequences
+    N: int = 0             # gather: D, the row length; attn: query heads
+    K: int = 0             # gather: pooling factor (rows per bag); attn: context tokens per sequence
     relu: bool = True
     n_floats: int = 0      # triad
-    rows: int = 0          # gather: rows of the table
+    rows: int = 0          # gather: rows of the table; attn: KV heads
 
     @property
     def is_gemm(self) -> bool:
@@ -46,6 +54,8 @@ class Op:
     def flops(self) -> float:
         if self.kind == "gather":
             return 1.0 * self.M * self.K * self.N                 # one add per gathered element
+        if self.kind == "attn":                                   # q . K^T and P . V, a multiply-add each
+            return 4.0 * self.M * self.N * self.K * ATTN_HEAD_DIM
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -56,6 +66,9 @@ class Op:
             return 1.0 * (self.M * self.K + self.N * self.K) + 2.0 * self.M * self.N
         if self.kind == "gather":                                 # rows read, indices, offsets, output
             return 2.0 * self.M * self.K * self.N + 4.0 * self.M * self.K + 4.0 * (self.M + 1) + 2.0 * self.M * self.N
+        if self.kind == "attn":                                   # K and V, q and out, block table, ctx_lens
+            return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.N * ATTN_HEAD_DIM
+                    + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M)
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -127,6 +140,13 @@ INDEX: Dict[str, int] = {n: i for i, n in enumerate(NAMES)}
 #                    come from HBM), then two bf16 GEMMs (the top MLP over the 26 x 128 pooled
 #                    features).  The gather is a third kernel character (indexed rows); no co-run
 #                    groups are measured with it yet
+#   llm_decode_256   one Llama-8B-like decoder layer in the decode phase at batch 256: the fused QKV
+#                    projection (256 x 6144 x 4096), decode attention of 32 query heads over 8 KV
+#                    heads (groups of 4) with 1,024 tokens of context per sequence, the output
+#                    projection (256 x 4096 x 4096).  The paged KV cache is exactly 1 GiB (256 x 32
+#                    blocks x 8 heads x 2 x 8 KiB) -- four times the Infinity Cache, like the DLRM
+#                    table -- so it streams from HBM, through a shuffled block table.  The attention
+#                    is a fourth kernel character; no co-run groups are measured with it yet
 EXTRA: Dict[str, Workload] = {
     "fp8_llm_2048": Workload("fp8_llm_2048", "llm_fp8", "hip", 2048, (Op("gemm8", 2048, 4096, 4096),) * 3, 1.0),
     "triad_only_2048": Workload("triad_only_2048", "stream", "hip", 2048,
@@ -134,6 +154,9 @@ EXTRA: Dict[str, Workload] = {
     "dlrm_2048": Workload("dlrm_2048", "dlrm", "hip", 2048,
                           (Op("gather", 2048 * 26, 128, 32, rows=4 * 1024 * 1024),
                            Op("gemm", 2048, 1024, 3328), Op("gemm", 2048, 1024, 1024)), 1.25),
+    "llm_decode_256": Workload("llm_decode_256", "llm_decode", "hip", 256,
+                               (Op("gemm", 256, 6144, 4096), Op("attn", 256, 32, 1024, rows=8),
+                                Op("gemm", 256, 4096, 4096)), 1.25),
 }
 
 
@@ -222,11 +245,19 @@ def default_gather_workgroups(B: int, blocks: int = 0) -> int:
     return blocks if 0 < blocks < need else need
 
 
+def default_attn_workgroups(S: int, Hkv: int) -> int:
+    """Workgroups the native decode-attention launch gets: one per (sequence, KV head) -- a
+    pure-Python copy of paged_decode_workgroups (native/hip/decode_attn.hip), pinned against it in
+    tests/test_decode_attn_cpu.py."""
+    return S * Hkv
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
     launches them for `cu_budget` under the default policy (default_gemm_workgroups), gather
-    workgroups as default_gather_workgroups counts them, the
+    workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups
+    count them, the
     stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
@@ -237,6 +268,8 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
             fo = min(1.0, default_gemm_workgroups(o.M, o.N, o.K, cu_budget, o.kind == "gemm8") / CUS)
         elif o.kind == "gather":
             fo = min(1.0, default_gather_workgroups(o.M) / CUS)
+        elif o.kind == "attn":
+            fo = min(1.0, default_attn_workgroups(o.M, o.rows) / CUS)
         else:
             fo = 1.0
         t += dt

@@ -1,14 +1,18 @@
-"""Torch-facing wrappers for the HIP load kernels (native/hip/loadgen.hip, native/hip/gather.hip).
+"""Torch-facing wrappers for the HIP load kernels (native/hip/loadgen.hip, native/hip/gather.hip,
+native/hip/decode_attn.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
 `embedding_bag(table, idx, offsets)` gathers indexed table rows and sums them per bag (random-row
-HBM / cache traffic, no MFMA).  Shapes are validated on the host before launch (the kernels
+HBM / cache traffic, no MFMA); `paged_decode_attention(q, k_cache, v_cache, block_table, ctx_lens)`
+is LLM decode attention over a paged KV cache (block-table-indexed HBM traffic, MFMA products, a
+softmax in the loop).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
 Operands may be views into larger allocations (row slices, column slices, padded rows).  The
-host checks enforce, and tests/test_gpu_kernels_exact.py and test_gpu_gather_exact.py rely on:
+host checks enforce, and tests/test_gpu_kernels_exact.py, test_gpu_gather_exact.py and
+test_gpu_decode_attn_exact.py rely on:
 
   * A, Bt: K-contiguous rows, the first element 16-byte aligned, the leading dimension (row
     stride in elements) >= K and a multiple of 8 for bf16, of 16 for fp8 -- every row then
@@ -28,11 +32,26 @@ host checks enforce, and tests/test_gpu_kernels_exact.py and test_gpu_gather_exa
     non-decreasing, offsets[0] >= 0, offsets[B] <= L), both contiguous, 4-byte aligned.  The
     kernel trusts the indices: check_indices=True verifies the offsets and 0 <= idx[j] < R for the
     j in [offsets[0], offsets[B]) -- the entries the bags name; the others are never read as
-    indices -- on the device first (one sync); a caller that passes False guarantees them itself.
+    indices -- on the device first (one sync); a caller that passes False guarantees them itself;
+  * paged_decode_attention: q and out bf16 [S, Hq, 128] with contiguous [Hq, 128] slabs, a sequence
+    stride >= Hq * 128 and a multiple of 8, the first element 16-byte aligned; k_cache bf16
+    [NB, Hkv, 32, 128] (a token's row d-contiguous) and v_cache bf16 [NB, Hkv, 128, 32]
+    (token-contiguous: the transposed V layout of paged-attention servers), both contiguous and
+    16-byte aligned; Hq / Hkv in {1, 2, 4, 8, 16}; block_table int32 [S, max_blocks] with
+    contiguous rows a stride >= max_blocks apart, ctx_lens int32 [S] contiguous, both 4-byte
+    aligned.  Token t of sequence s is slot t % 32 of block block_table[s, t // 32].  The kernel
+    trusts ctx_lens and the block ids: check=True verifies 0 <= ctx <= 32 * max_blocks and
+    0 <= id < NB for the ceil(ctx / 32) leading entries of each row -- the ones the sequence names;
+    the others are never read as block ids -- on the device first (one sync); a caller that passes
+    False guarantees them itself.
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
-[offsets[0], offsets[B]) and the offsets) and writes only the B x D window.
+[offsets[0], offsets[B]) and the offsets) and writes only the B x D window.  The decode attention
+reads q's S x Hq x 128 window, ctx_lens, the named table entries and the (block, KV head) slabs they
+name -- whole slabs, but the slots of a sequence's last block past ctx may hold anything (NaN
+included) without touching the output: their scores are replaced by -inf and their V elements by
+zero -- and writes only out's S x Hq x 128 window.
 
 Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
 of the conversion and float64 sums):
@@ -52,7 +71,15 @@ of the conversion and float64 sums):
   * without ReLU, -0.0 survives only where nothing is added to it: the GEMM epilogues compute
     acc + bias with acc = +0.0 for all-zero operands, so a bias of -0.0 gives +0.0; the gather
     starts every bag at +0.0, so an empty bag and a bag of a single -0.0 row give +0.0 (bit
-    pattern 0x0000); the triad's -0.0 + s * -0.0 is -0.0 for s > 0.
+    pattern 0x0000); the triad's -0.0 + s * -0.0 is -0.0 for s > 0;
+  * paged_decode_attention (pinned by tests/test_gpu_decode_attn_exact.py): q . k accumulates in
+    fp32 on the MFMA and scale multiplies the fp32 score (it is not folded into a bf16 q); the
+    softmax is the online one (running maximum) in fp32 with exp(x) = 2^(x * log2 e), so a
+    probability whose exponent is below fp32's range is exactly 0 and exp(0) exactly 1; the
+    normaliser is summed from the fp32 probabilities; the probabilities are rounded to bf16 for
+    the P . V MFMA (at most 2^-9 relative each), which accumulates in fp32; the partial results
+    of the four waves are merged in fp32, divided by the normaliser (an IEEE division) and rounded
+    to bf16 once.  ctx == 0 gives a row of +0.0.
 """
 from __future__ import annotations
 
@@ -258,6 +285,92 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torc
         if B:
             h.embedding_bag_bf16(table.data_ptr(), idx.data_ptr(), offsets.data_ptr(), out.data_ptr(), B, D,
                                  ld_table, ld_out, int(blocks), sp)
+    return out
+
+
+ATTN_HEAD_DIM, ATTN_BLOCK_TOKENS = 128, 32
+ATTN_GROUPS = (1, 2, 4, 8, 16)          # query heads per KV head (the MFMA's 16 columns hold a group)
+
+
+def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                           ctx_lens: torch.Tensor, out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                           stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
+    """out[s, h, :] = bf16(softmax_t(scale * q[s, h, :] . K[t, g, :]) . V[t, g, :]) over the ctx_lens[s]
+    tokens of sequence s, g = h // (Hq // Hkv): one new token per sequence against a paged KV cache.
+    Token t is slot t % 32 of block block_table[s, t // 32]; k_cache [NB, Hkv, 32, 128], v_cache
+    [NB, Hkv, 128, 32].  scale defaults to 1 / sqrt(128).  ctx_lens[s] == 0 gives a row of +0.0.
+    check=False skips the device-side check of ctx_lens and the block ids (and its sync): for
+    callers that guarantee them, and under graph capture."""
+    _check_devices("paged_decode_attention", q, k_cache, v_cache, block_table, ctx_lens, out)
+    if q.dtype != torch.bfloat16 or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16:
+        raise TypeError("paged_decode_attention expects bf16 q, k_cache and v_cache")
+    if block_table.dtype != torch.int32 or ctx_lens.dtype != torch.int32:
+        raise TypeError("paged_decode_attention expects an int32 block_table and ctx_lens")
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 or block_table.dim() != 2 or ctx_lens.dim() != 1:
+        raise ValueError("paged_decode_attention expects q [S, Hq, 128], k_cache [NB, Hkv, 32, 128], "
+                         "v_cache [NB, Hkv, 128, 32], block_table [S, max_blocks] and ctx_lens [S]")
+    S, Hq, D = q.shape
+    NB, Hkv, T, Dk = k_cache.shape
+    if D != ATTN_HEAD_DIM or Dk != ATTN_HEAD_DIM or v_cache.shape[2] != ATTN_HEAD_DIM:
+        raise ValueError(f"paged_decode_attention: the head dim must be {ATTN_HEAD_DIM}")
+    if T != ATTN_BLOCK_TOKENS or v_cache.shape[3] != ATTN_BLOCK_TOKENS:
+        raise ValueError(f"paged_decode_attention: the cache block size must be {ATTN_BLOCK_TOKENS} tokens")
+    if tuple(v_cache.shape) != (NB, Hkv, ATTN_HEAD_DIM, ATTN_BLOCK_TOKENS):
+        raise ValueError(f"paged_decode_attention: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} "
+                         "disagree on the blocks or the KV heads")
+    if Hkv <= 0 or Hq % Hkv or Hq // Hkv not in ATTN_GROUPS:
+        raise ValueError(f"paged_decode_attention: Hq / Hkv = {Hq} / {Hkv} must be one of {ATTN_GROUPS}")
+    if not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError("paged_decode_attention expects contiguous caches")
+    if k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
+        raise ValueError("paged_decode_attention: the caches must be 16-byte aligned")
+    if block_table.shape[0] != S or ctx_lens.shape[0] != S:
+        raise ValueError(f"paged_decode_attention: block_table {tuple(block_table.shape)} / ctx_lens "
+                         f"{tuple(ctx_lens.shape)} do not match the {S} sequences of q")
+    max_blocks = block_table.shape[1]
+    if max_blocks > 1 and block_table.stride(1) != 1:
+        raise ValueError("paged_decode_attention expects contiguous block_table rows")
+    if S > 1 and block_table.stride(0) < max_blocks:
+        raise ValueError(f"paged_decode_attention: block_table row stride {block_table.stride(0)} must be >= {max_blocks}")
+    if S > 1 and ctx_lens.stride(0) != 1:
+        raise ValueError("paged_decode_attention expects contiguous ctx_lens")
+    if S * Hkv >= 2 ** 31 or NB * Hkv >= 2 ** 31:
+        raise ValueError("paged_decode_attention: more than 2^31 - 1 workgroups or cache slabs")
+    if out is None:
+        out = torch.empty((S, Hq, D), dtype=torch.bfloat16, device=q.device)
+    if out.dim() != 3 or tuple(out.shape) != (S, Hq, D) or out.dtype != torch.bfloat16:
+        raise ValueError("bad output tensor")
+    slab = Hq * ATTN_HEAD_DIM
+    for name, t in (("q", q), ("out", out)):
+        if t.stride(2) != 1 or (Hq > 1 and t.stride(1) != ATTN_HEAD_DIM):
+            raise ValueError(f"paged_decode_attention: {name} must have contiguous [Hq, {ATTN_HEAD_DIM}] slabs")
+        if S > 1 and (t.stride(0) < slab or t.stride(0) % 8):
+            raise ValueError(f"paged_decode_attention: {name} sequence stride {t.stride(0)} must be >= {slab} "
+                             "and a multiple of 8")
+        if t.data_ptr() % 16:
+            raise ValueError(f"paged_decode_attention: {name} must be 16-byte aligned")
+    ld_q = q.stride(0) if S > 1 else slab
+    ld_out = out.stride(0) if S > 1 else slab
+    ld_table = block_table.stride(0) if S > 1 else max_blocks
+    if scale is None:
+        scale = ATTN_HEAD_DIM ** -0.5
+    if S == 0:
+        return out
+    h = _native.hip()
+    with torch.cuda.device(q.device):
+        sp = _stream_ptr(stream, q.device)
+        if check:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(q.device)):
+                need = (ctx_lens + (ATTN_BLOCK_TOKENS - 1)) // ATTN_BLOCK_TOKENS
+                named = torch.arange(max_blocks, dtype=torch.int32, device=q.device)[None, :] < need[:, None]
+                bad = torch.stack([((ctx_lens < 0) | (ctx_lens > ATTN_BLOCK_TOKENS * max_blocks)).any(),
+                                   (((block_table < 0) | (block_table >= NB)) & named).any()]).tolist()    # the one sync
+            if bad[0]:
+                raise ValueError(f"paged_decode_attention: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
+            if bad[1]:
+                raise ValueError(f"paged_decode_attention: a block id is outside [0, {NB})")
+        h.paged_decode_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
+                            ctx_lens.data_ptr(), out.data_ptr(), S, Hq, Hkv, ld_q, ld_out, ld_table, float(scale), sp)
     return out
 
 

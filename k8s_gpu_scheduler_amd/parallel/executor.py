@@ -46,6 +46,7 @@ class PodRun:
 
 
 GATHER_BLOCK_ROWS = 4096          # rows of the CPU-generated block a gather table repeats
+ATTN_PATTERN_BLOCKS = 64          # KV-cache blocks of the CPU-generated pattern an attention cache repeats
 
 
 class _Buffers:
@@ -78,6 +79,30 @@ class _Buffers:
                 offsets = (torch.arange(o.M + 1, dtype=torch.int32) * o.K).to(device)
                 out = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
                 self.ops.append((o, (out, table, idx, offsets)))
+            elif o.kind == "attn":
+                # M sequences of K context tokens, N query heads over o.rows KV heads, in a paged
+                # cache of M * K / 32 blocks that a seeded random permutation deals out to the
+                # sequences.  The caches are one small CPU-generated pattern repeated on the device
+                # (no GiB on the host), values k / 64 with |k| <= 127
+                T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
+                if o.K % T:
+                    raise ValueError(f"workload {w.name}: attention context {o.K} is no multiple of {T}")
+                per_seq = o.K // T
+                nb = o.M * per_seq
+                n = min(nb, ATTN_PATTERN_BLOCKS)
+                q = torch.randn(o.M, o.N, D, generator=g).to(torch.bfloat16).to(device)
+                caches = []
+                for shape in ((o.rows, T, D), (o.rows, D, T)):
+                    pat = (torch.randint(-127, 128, (n,) + shape, generator=g).float() / 64).to(torch.bfloat16).to(device)
+                    c = torch.empty((nb,) + shape, dtype=torch.bfloat16, device=device)
+                    full = nb // n * n
+                    c[:full].view(-1, n, *shape).copy_(pat)
+                    c[full:].copy_(pat[:nb - full])
+                    caches.append(c)
+                table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
+                ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
+                out = torch.empty(o.M, o.N, D, dtype=torch.bfloat16, device=device)
+                self.ops.append((o, (out, q, caches[0], caches[1], table, ctx)))
             elif o.kind == "triad":
                 x = torch.ones(o.n_floats, dtype=torch.float32, device=device)
                 y = torch.ones(o.n_floats, dtype=torch.float32, device=device)
@@ -102,6 +127,10 @@ def enqueue_ops(bufs: _Buffers, iters: int, st, budget: int, blocks: int = 0) ->
                 # the indices were generated in range: no check, no sync (this runs under capture)
                 out, table, idx, offsets = t
                 loadgen.embedding_bag(table, idx, offsets, out=out, stream=st, check_indices=False)
+            elif o.kind == "attn":
+                # ctx_lens and the block ids are in range by construction: no check, no sync (capture)
+                out, q, kc, vc, table, ctx = t
+                loadgen.paged_decode_attention(q, kc, vc, table, ctx, out=out, stream=st, check=False)
             elif o.kind == "triad":
                 x, y, z = t
                 loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)

@@ -36,6 +36,14 @@ void embedding_bag_bf16(uintptr_t table, uintptr_t idx, uintptr_t offsets, uintp
                         int64_t ld_table, int64_t ld_out, int blocks, uintptr_t stream);
 // workgroups of that launch
 int embedding_bag_workgroups(int B, int blocks);
+// out[s, h, :] = bf16(softmax(scale * q[s, h, :] . K^T) . V) over the ctx_lens[s] tokens block_table[s, :]
+// names -- native/hip/decode_attn.hip; k_cache [NB, Hkv, 32, 128], v_cache [NB, Hkv, 128, 32], q / out
+// [S, Hq, 128] with sequence strides ld_q / ld_out, block_table rows ld_table apart (strides in elements)
+void paged_decode_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t block_table, uintptr_t ctx_lens,
+                       uintptr_t out, int S, int Hq, int Hkv, int64_t ld_q, int64_t ld_out, int64_t ld_table,
+                       float scale, uintptr_t stream);
+// workgroups of that launch: one per (sequence, KV head)
+int paged_decode_workgroups(int S, int Hkv);
 void set_triad_variant(int v);
 void set_gemm_tile(int t);
 void set_w4_probe(int mask);

@@ -65,6 +65,11 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("out"), py::arg("B"), py::arg("D"), py::arg("ld_table"), py::arg("ld_out"), py::arg("blocks"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
   m.def("embedding_bag_workgroups", &gs::embedding_bag_workgroups, py::arg("B"), py::arg("blocks") = 0);
+  m.def("paged_decode_bf16", &gs::paged_decode_bf16, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_table"), py::arg("ctx_lens"), py::arg("out"), py::arg("S"), py::arg("Hq"), py::arg("Hkv"),
+        py::arg("ld_q"), py::arg("ld_out"), py::arg("ld_table"), py::arg("scale"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("paged_decode_workgroups", &gs::paged_decode_workgroups, py::arg("S"), py::arg("Hkv"));
   m.def("set_triad_variant", &gs::set_triad_variant, py::arg("variant"));
   m.def("set_gemm_tile", &gs::set_gemm_tile, py::arg("tile"));
   m.def("set_w4_probe", &gs::set_w4_probe, py::arg("mask"));
