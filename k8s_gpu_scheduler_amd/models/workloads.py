@@ -200,7 +200,8 @@ CUS = 256                          # MI355X compute units
 POD_CU_BUDGET = 64                 # a bench pod's GEMM tile budget (2 CU-slice units x 32 CUs)
 
 
-# block tile (BM, BN) of the native GEMM kernels (native/hip/loadgen.hip kTileBM / kTileBN)
+# block tile (BM, BN) of the native GEMM kernels: the rows of the kTiles table (native/hip/gemm.hip)
+# the default policy can pick
 _TILE = {1: (128, 128), 2: (64, 128), 3: (64, 64), 4: (256, 256), 10: (256, 256)}
 
 
@@ -208,7 +209,7 @@ def default_gemm_workgroups(M: int, N: int, K: int, cu_budget: int = 0, fp8: boo
     """Workgroups the native GEMM launches for this shape under the DEFAULT kernel policy
     (policy 10, or 1: the same grids -- tile 14 launches tile 10's; no forced tile, split-K off)
     -- a pure-Python copy of pick_gemm_tile /
-    resolve_gemm_tile / fp8_tile_128 (native/hip/loadgen.hip), so the CU-fill feature needs no
+    resolve_gemm_tile / fp8_tile_128 (native/hip/gemm.hip), so the CU-fill feature needs no
     HIP build and never reads the process-wide tile settings.  Pinned against the
     native picker in tests/test_gemm_policy_picker.py."""
     alone = cu_budget <= 0 or cu_budget >= CUS

@@ -1,5 +1,5 @@
-"""Torch-facing wrappers for the HIP load kernels (native/hip/loadgen.hip, native/hip/gather.hip,
-native/hip/decode_attn.hip).
+"""Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
+headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;

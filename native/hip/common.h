@@ -1,6 +1,7 @@
 // Shared helpers for the HIP native module (gfx950 / MI355X only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 
@@ -15,4 +16,8 @@ namespace gs {
 constexpr int kWave = 64;
 constexpr int kXcds = 8;
 constexpr int kCus = 256;
+
+inline void check_align(const void* p, const char* what) {
+  if (reinterpret_cast<uintptr_t>(p) % 16 != 0) throw std::runtime_error(std::string(what) + " must be 16-byte aligned");
+}
 }  // namespace gs

@@ -1,7 +1,7 @@
 
 
 def _tile_coords(b, nwg, tiles_m, tiles_n, xmap, xcds=8):
-    """Python twin of loadgen.hip tile_coords (the device-side block -> tile map)."""
+    """Python twin of gemm_device.h tile_coords (the device-side block -> tile map)."""
     xcd = b % xcds
     q, rem = divmod(nwg, xcds)
     wgid = (xcd * (q + 1) if xcd < rem else rem * (q + 1) + (xcd - rem) * q) + b // xcds
