@@ -75,6 +75,17 @@ class Op:
         """MFMA throughput relative to bf16 (the fp8 MFMA does twice the work per clock)."""
         return 2.0 if self.kind == "gemm8" else 1.0
 
+    def workgroups(self, cu_budget: int) -> Optional[int]:
+        """Workgroups of the op's launch under the default kernel policy (GEMM tiles picked for
+        `cu_budget` CUs, 0 = the whole chip); None: the stream kernel's 8192 blocks fill any chip."""
+        if self.is_gemm:
+            return default_gemm_workgroups(self.M, self.N, self.K, cu_budget, self.kind == "gemm8")
+        if self.kind == "gather":
+            return default_gather_workgroups(self.M)
+        if self.kind == "attn":
+            return default_attn_workgroups(self.M, self.rows)
+        return None
+
 
 @dataclass(frozen=True)
 class Workload:
@@ -265,16 +276,9 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     t = f = 0.0
     for o in w.ops:
         dt = roofline_seconds(Workload(w.name, w.family, w.framework, w.batch, (o,), 0.0), 1.0)
-        if o.is_gemm:
-            fo = min(1.0, default_gemm_workgroups(o.M, o.N, o.K, cu_budget, o.kind == "gemm8") / CUS)
-        elif o.kind == "gather":
-            fo = min(1.0, default_gather_workgroups(o.M) / CUS)
-        elif o.kind == "attn":
-            fo = min(1.0, default_attn_workgroups(o.M, o.rows) / CUS)
-        else:
-            fo = 1.0
+        wg = o.workgroups(cu_budget)
         t += dt
-        f += dt * fo
+        f += dt * (1.0 if wg is None else min(1.0, wg / CUS))
     return f / t if t > 0 else None
 
 

@@ -88,6 +88,7 @@ from typing import Optional
 import torch
 
 from .. import _native
+from ..models.workloads import ATTN_BLOCK_TOKENS, ATTN_HEAD_DIM          # the decode-attention kernel's fixed sizes
 
 BM, BN, BK = 64, 64, 64          # minimum granularity; the tile (128x128 / 64x128 / 64x64) is picked per shape
 
@@ -116,26 +117,42 @@ def _check_devices(name: str, *ts: Optional[torch.Tensor]) -> torch.device:
     return dev
 
 
-def check_gemm_shapes(M: int, N: int, K: int) -> None:
-    if M <= 0 or N <= 0 or K <= 0 or M % BM or N % BN or K % BK:
-        raise ValueError(f"gemm shape ({M},{N},{K}) must be positive multiples of ({BM},{BN},{BK})")
+def _launch_stream(stream: Optional[torch.cuda.Stream], device: torch.device):
+    """The launch stream (the caller's, or the device's current one) as a context: torch work
+    inside it -- an allocation, a check -- is ordered with the kernel."""
+    return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device))
 
 
-def gemm(a: torch.Tensor, bt: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-         relu: bool = False, stream: Optional[torch.cuda.Stream] = None, cu_budget: int = 0) -> torch.Tensor:
-    """out[M,N] = act(a[M,K] @ bt[N,K]^T + bias[N]) -- bf16 in/out, fp32 accumulate.
-    cu_budget: CUs this GEMM can expect to own (the pod's share when pods co-run; 0 = the
-    whole chip) -- steers the tile choice (native pick_gemm_tile)."""
-    if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16:
-        raise TypeError("gemm expects bf16 operands")
-    _check_devices("gemm", a, bt, out, bias)
+def _row_stride(t: torch.Tensor, rows: int, default: int) -> int:
+    """The stride of dim 0 in elements; of a single row torch may report anything: the default."""
+    return t.stride(0) if rows > 1 else default
+
+
+def check_gemm_shapes(M: int, N: int, K: int, bk: int = BK, name: str = "gemm") -> None:
+    if M <= 0 or N <= 0 or K <= 0 or M % BM or N % BN or K % bk:
+        raise ValueError(f"{name} shape ({M},{N},{K}) must be positive multiples of ({BM},{BN},{bk})")
+
+
+FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950), not the MI300 "fnuz" encoding
+_OPERAND_NAMES = {torch.bfloat16: "bf16", FP8: "float8_e4m3fn"}
+
+
+def _gemm_operands(name: str, dtype: torch.dtype, bk: int, rows16: bool, a: torch.Tensor, bt: torch.Tensor,
+                   out: Optional[torch.Tensor], bias: Optional[torch.Tensor]):
+    """The checks `gemm` and `gemm_fp8` share: operands of `dtype` (K a multiple of `bk`, row
+    strides multiples of 16 elements with `rows16`), the output (made when None) and the bias.
+    Returns (M, N, K, out, the bias pointer or 0)."""
+    if a.dtype != dtype or bt.dtype != dtype:
+        raise TypeError(f"{name} expects {_OPERAND_NAMES[dtype]} operands")
+    _check_devices(name, a, bt, out, bias)
     if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
-        raise ValueError(f"gemm shape mismatch {tuple(a.shape)} x {tuple(bt.shape)}^T")
-    if a.stride(1) != 1 or bt.stride(1) != 1:
-        raise ValueError("gemm expects row-major (K-contiguous) operands")
+        raise ValueError(f"{name} shape mismatch {tuple(a.shape)} x {tuple(bt.shape)}^T")
+    if a.stride(1) != 1 or bt.stride(1) != 1 or (rows16 and (a.stride(0) % 16 or bt.stride(0) % 16)):
+        raise ValueError(f"{name} expects row-major operands with 16-byte aligned rows" if rows16 else
+                         f"{name} expects row-major (K-contiguous) operands")
     M, K = a.shape
     N = bt.shape[0]
-    check_gemm_shapes(M, N, K)
+    check_gemm_shapes(M, N, K, bk, name)
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     if out.shape != (M, N) or out.dtype != torch.bfloat16 or out.stride(1) != 1:
@@ -145,6 +162,15 @@ def gemm(a: torch.Tensor, bt: torch.Tensor, out: Optional[torch.Tensor] = None, 
         if bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous():
             raise ValueError("bias must be a contiguous fp32 vector of length N")
         bptr = bias.data_ptr()
+    return M, N, K, out, bptr
+
+
+def gemm(a: torch.Tensor, bt: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+         relu: bool = False, stream: Optional[torch.cuda.Stream] = None, cu_budget: int = 0) -> torch.Tensor:
+    """out[M,N] = act(a[M,K] @ bt[N,K]^T + bias[N]) -- bf16 in/out, fp32 accumulate.
+    cu_budget: CUs this GEMM can expect to own (the pod's share when pods co-run; 0 = the
+    whole chip) -- steers the tile choice (native pick_gemm_tile)."""
+    M, N, K, out, bptr = _gemm_operands("gemm", torch.bfloat16, BK, False, a, bt, out, bias)
     h = _native.hip()
     with torch.cuda.device(a.device):
         sp = _stream_ptr(stream, a.device)
@@ -154,14 +180,11 @@ def gemm(a: torch.Tensor, bt: torch.Tensor, out: Optional[torch.Tensor] = None, 
         wsf = h.splitk_workspace_floats(M, N, K, cu_budget)
         ws = None
         if wsf:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(a.device)):
+            with _launch_stream(stream, a.device):
                 ws = torch.empty(wsf, dtype=torch.float32, device=a.device)
         h.gemm_bf16_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), bptr, M, N, K, a.stride(0), bt.stride(0),
                        out.stride(0), relu, sp, cu_budget, ws.data_ptr() if ws is not None else 0, wsf)
     return out
-
-
-FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950), not the MI300 "fnuz" encoding
 
 
 def gemm_fp8(a: torch.Tensor, bt: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -169,26 +192,7 @@ def gemm_fp8(a: torch.Tensor, bt: torch.Tensor, out: Optional[torch.Tensor] = No
              cu_budget: int = 0) -> torch.Tensor:
     """out[M,N] = act(a[M,K] @ bt[N,K]^T + bias[N]) -- e4m3fn operands, fp32 accumulate, bf16
     out, on the block-scaled fp8 MFMA (unit scales).  M, N multiples of 64, K of 128."""
-    if a.dtype != FP8 or bt.dtype != FP8:
-        raise TypeError("gemm_fp8 expects float8_e4m3fn operands")
-    _check_devices("gemm_fp8", a, bt, out, bias)
-    if a.dim() != 2 or bt.dim() != 2 or a.shape[1] != bt.shape[1]:
-        raise ValueError(f"gemm_fp8 shape mismatch {tuple(a.shape)} x {tuple(bt.shape)}^T")
-    if a.stride(1) != 1 or bt.stride(1) != 1 or a.stride(0) % 16 or bt.stride(0) % 16:
-        raise ValueError("gemm_fp8 expects row-major operands with 16-byte aligned rows")
-    M, K = a.shape
-    N = bt.shape[0]
-    if M <= 0 or N <= 0 or K <= 0 or M % 64 or N % 64 or K % 128:
-        raise ValueError(f"gemm_fp8 shape ({M},{N},{K}) must be positive multiples of (64,64,128)")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    if out.shape != (M, N) or out.dtype != torch.bfloat16 or out.stride(1) != 1:
-        raise ValueError("bad output tensor")
-    bptr = 0
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous():
-            raise ValueError("bias must be a contiguous fp32 vector of length N")
-        bptr = bias.data_ptr()
+    M, N, K, out, bptr = _gemm_operands("gemm_fp8", FP8, 128, True, a, bt, out, bias)
     with torch.cuda.device(a.device):
         _native.hip().gemm_fp8_nt(a.data_ptr(), bt.data_ptr(), out.data_ptr(), bptr, M, N, K, a.stride(0),
                                   bt.stride(0), out.stride(0), relu, _stream_ptr(stream, a.device), cu_budget)
@@ -267,13 +271,12 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torc
         raise ValueError(f"embedding_bag: output row stride {out.stride(0)} must be >= D and a multiple of 8")
     if out.data_ptr() % 16:
         raise ValueError("embedding_bag: out must be 16-byte aligned")
-    ld_table = table.stride(0) if R > 1 else D
-    ld_out = out.stride(0) if B > 1 else D
+    ld_table, ld_out = _row_stride(table, R, D), _row_stride(out, B, D)
     h = _native.hip()
     with torch.cuda.device(table.device):
         sp = _stream_ptr(stream, table.device)
         if check_indices:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(table.device)):
+            with _launch_stream(stream, table.device):
                 pos = torch.arange(L, dtype=torch.int32, device=idx.device)
                 named = (pos >= offsets[0]) & (pos < offsets[-1])      # only these are read as indices
                 bad = torch.stack([(((idx < 0) | (idx >= R)) & named).any(), (offsets[1:] < offsets[:-1]).any(),
@@ -288,7 +291,6 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torc
     return out
 
 
-ATTN_HEAD_DIM, ATTN_BLOCK_TOKENS = 128, 32
 ATTN_GROUPS = (1, 2, 4, 8, 16)          # query heads per KV head (the MFMA's 16 columns hold a group)
 
 
@@ -349,9 +351,7 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
                              "and a multiple of 8")
         if t.data_ptr() % 16:
             raise ValueError(f"paged_decode_attention: {name} must be 16-byte aligned")
-    ld_q = q.stride(0) if S > 1 else slab
-    ld_out = out.stride(0) if S > 1 else slab
-    ld_table = block_table.stride(0) if S > 1 else max_blocks
+    ld_q, ld_out, ld_table = _row_stride(q, S, slab), _row_stride(out, S, slab), _row_stride(block_table, S, max_blocks)
     if scale is None:
         scale = ATTN_HEAD_DIM ** -0.5
     if S == 0:
@@ -360,7 +360,7 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
     with torch.cuda.device(q.device):
         sp = _stream_ptr(stream, q.device)
         if check:
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(q.device)):
+            with _launch_stream(stream, q.device):
                 need = (ctx_lens + (ATTN_BLOCK_TOKENS - 1)) // ATTN_BLOCK_TOKENS
                 named = torch.arange(max_blocks, dtype=torch.int32, device=q.device)[None, :] < need[:, None]
                 bad = torch.stack([((ctx_lens < 0) | (ctx_lens > ATTN_BLOCK_TOKENS * max_blocks)).any(),

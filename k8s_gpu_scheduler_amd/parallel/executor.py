@@ -49,93 +49,142 @@ GATHER_BLOCK_ROWS = 4096          # rows of the CPU-generated block a gather tab
 ATTN_PATTERN_BLOCKS = 64          # KV-cache blocks of the CPU-generated pattern an attention cache repeats
 
 
+def _repeat(pattern: torch.Tensor, n: int) -> torch.Tensor:
+    """n entries that cycle through `pattern`'s (along dim 0): one small CPU-generated block
+    repeated on the device, so a GiB operand never exists on the host."""
+    out = torch.empty((n,) + pattern.shape[1:], dtype=pattern.dtype, device=pattern.device)
+    full = n - n % len(pattern)
+    out[:full].view(-1, *pattern.shape).copy_(pattern)
+    out[full:].copy_(pattern[:n - full])
+    return out
+
+
+def _gemm_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    a = ((torch.rand(o.M, o.K, generator=g) * 2 - 1).to(torch.bfloat16)).to(device)
+    bt = ((torch.rand(o.N, o.K, generator=g) * 2 - 1).to(torch.bfloat16) * 0.05).to(device)
+    if o.kind == "gemm8":                   # e4m3 operands (weights scaled into range)
+        a, bt = a.to(loadgen.FP8), (bt * 16).to(loadgen.FP8)
+    bias = torch.zeros(o.N, dtype=torch.float32, device=device)
+    c = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
+    return a, bt, bias, c
+
+
+def _gather_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """M bags of K rows of N elements out of a table of o.rows rows.  The table repeats one block
+    of values k / 128, |k| <= 127: every fp32 partial sum of a bag is exact, so the output does
+    not depend on the kernel's summation order."""
+    n = min(o.rows, GATHER_BLOCK_ROWS)
+    blk = ((torch.randint(-127, 128, (n, o.N), generator=g).float() / 128).to(torch.bfloat16)).to(device)
+    table = _repeat(blk, o.rows)
+    idx = torch.randint(o.rows, (o.M * o.K,), generator=g, dtype=torch.int32).to(device)
+    offsets = (torch.arange(o.M + 1, dtype=torch.int32) * o.K).to(device)
+    out = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
+    return out, table, idx, offsets
+
+
+def _attn_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """M sequences of K context tokens, N query heads over o.rows KV heads, in a paged cache of
+    M * K / 32 blocks that a seeded random permutation deals out to the sequences.  The caches
+    repeat one pattern of values k / 64, |k| <= 127."""
+    T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
+    if o.K % T:
+        raise ValueError(f"attention context {o.K} is no multiple of {T}")
+    per_seq = o.K // T
+    nb = o.M * per_seq
+    n = min(nb, ATTN_PATTERN_BLOCKS)
+    q = torch.randn(o.M, o.N, D, generator=g).to(torch.bfloat16).to(device)
+
+    def cache(*shape: int) -> torch.Tensor:
+        pat = (torch.randint(-127, 128, (n,) + shape, generator=g).float() / 64).to(torch.bfloat16).to(device)
+        return _repeat(pat, nb)
+    kc, vc = cache(o.rows, T, D), cache(o.rows, D, T)
+    table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
+    ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
+    out = torch.empty(o.M, o.N, D, dtype=torch.bfloat16, device=device)
+    return out, q, kc, vc, table, ctx
+
+
+def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    return tuple(torch.ones(o.n_floats, dtype=torch.float32, device=device) for _ in range(3))
+
+
+# The launches look their loadgen entry point up when called (tests replace the attributes).  The
+# gather's indices, and the attention's ctx_lens and block ids, are in range by construction: no
+# check, no sync (this runs under graph capture).
+def _launch_gemm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    a, bt, bias, c = t
+    loadgen.gemm(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
+
+
+def _launch_gemm8(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    a, bt, bias, c = t
+    loadgen.gemm_fp8(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
+
+
+def _launch_gather(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, table, idx, offsets = t
+    loadgen.embedding_bag(table, idx, offsets, out=out, stream=st, check_indices=False)
+
+
+def _launch_attn(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, q, kc, vc, table, ctx = t
+    loadgen.paged_decode_attention(q, kc, vc, table, ctx, out=out, stream=st, check=False)
+
+
+def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    x, y, z = t
+    loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
+
+
+# What the executor knows of an op kind: kind -> (make(o, g, device) -> the operand tuple, drawing
+# from the CPU generator g; launch(o, t, st, budget, blocks), the kind's one loadgen call; the
+# position of the output in the tuple).  Operand layouts: GEMMs (a, bt, bias, c); gather (out,
+# table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); triad (x, y, z), x = y + s z.
+OP_KINDS = {
+    "gemm": (_gemm_operands, _launch_gemm, 3),
+    "gemm8": (_gemm_operands, _launch_gemm8, 3),
+    "gather": (_gather_operands, _launch_gather, 0),
+    "attn": (_attn_operands, _launch_attn, 0),
+    "triad": (_triad_operands, _launch_triad, 0),
+}
+
+
+def _kind(o: Op) -> tuple:
+    try:
+        return OP_KINDS[o.kind]
+    except KeyError:
+        raise ValueError(f"unknown op kind {o.kind!r}") from None
+
+
 class _Buffers:
     def __init__(self, w: Workload, device: torch.device):
-        self.ops: List[Tuple[Op, tuple]] = []
         # (a CRC of the name, not hash(): str hashes change from process to process, and two runs
         # of the bench must feed the kernels the same operands)
         g = torch.Generator(device="cpu").manual_seed(zlib.crc32(w.name.encode()) & 0xFFFF)
-        for o in w.ops:
-            if o.is_gemm:
-                a = ((torch.rand(o.M, o.K, generator=g) * 2 - 1).to(torch.bfloat16)).to(device)
-                bt = ((torch.rand(o.N, o.K, generator=g) * 2 - 1).to(torch.bfloat16) * 0.05).to(device)
-                if o.kind == "gemm8":                   # e4m3 operands (weights scaled into range)
-                    a, bt = a.to(loadgen.FP8), (bt * 16).to(loadgen.FP8)
-                bias = torch.zeros(o.N, dtype=torch.float32, device=device)
-                c = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
-                self.ops.append((o, (a, bt, bias, c)))
-            elif o.kind == "gather":
-                # M bags of K rows of N elements out of a table of o.rows rows.  The table is one
-                # small CPU-generated block repeated on the device (no GiB on the host); its values
-                # are k / 128, |k| <= 127: every fp32 partial sum of a bag is exact, so the output
-                # does not depend on the kernel's summation order
-                n = min(o.rows, GATHER_BLOCK_ROWS)
-                blk = ((torch.randint(-127, 128, (n, o.N), generator=g).float() / 128).to(torch.bfloat16)).to(device)
-                table = torch.empty(o.rows, o.N, dtype=torch.bfloat16, device=device)
-                full = o.rows // n * n
-                table[:full].view(-1, n, o.N).copy_(blk)
-                table[full:].copy_(blk[:o.rows - full])
-                idx = torch.randint(o.rows, (o.M * o.K,), generator=g, dtype=torch.int32).to(device)
-                offsets = (torch.arange(o.M + 1, dtype=torch.int32) * o.K).to(device)
-                out = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
-                self.ops.append((o, (out, table, idx, offsets)))
-            elif o.kind == "attn":
-                # M sequences of K context tokens, N query heads over o.rows KV heads, in a paged
-                # cache of M * K / 32 blocks that a seeded random permutation deals out to the
-                # sequences.  The caches are one small CPU-generated pattern repeated on the device
-                # (no GiB on the host), values k / 64 with |k| <= 127
-                T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
-                if o.K % T:
-                    raise ValueError(f"workload {w.name}: attention context {o.K} is no multiple of {T}")
-                per_seq = o.K // T
-                nb = o.M * per_seq
-                n = min(nb, ATTN_PATTERN_BLOCKS)
-                q = torch.randn(o.M, o.N, D, generator=g).to(torch.bfloat16).to(device)
-                caches = []
-                for shape in ((o.rows, T, D), (o.rows, D, T)):
-                    pat = (torch.randint(-127, 128, (n,) + shape, generator=g).float() / 64).to(torch.bfloat16).to(device)
-                    c = torch.empty((nb,) + shape, dtype=torch.bfloat16, device=device)
-                    full = nb // n * n
-                    c[:full].view(-1, n, *shape).copy_(pat)
-                    c[full:].copy_(pat[:nb - full])
-                    caches.append(c)
-                table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
-                ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
-                out = torch.empty(o.M, o.N, D, dtype=torch.bfloat16, device=device)
-                self.ops.append((o, (out, q, caches[0], caches[1], table, ctx)))
-            elif o.kind == "triad":
-                x = torch.ones(o.n_floats, dtype=torch.float32, device=device)
-                y = torch.ones(o.n_floats, dtype=torch.float32, device=device)
-                z = torch.ones(o.n_floats, dtype=torch.float32, device=device)
-                self.ops.append((o, (x, y, z)))
-            else:
-                raise ValueError(f"workload {w.name}: unknown op kind {o.kind!r}")
+        try:
+            self.ops: List[Tuple[Op, tuple]] = [(o, _kind(o)[0](o, g, device)) for o in w.ops]
+        except ValueError as e:
+            raise ValueError(f"workload {w.name}: {e}") from None
+
+
+def enqueue_op(o: Op, t: tuple, st, budget: int, blocks: int = 0) -> None:
+    """One op on stream `st`, on the operands `t` that _Buffers made for it."""
+    _kind(o)[1](o, t, st, budget, blocks)
+
+
+def op_output(o: Op, t: tuple) -> torch.Tensor:
+    """The tensor of `t` that the op's kernel writes."""
+    return t[_kind(o)[2]]
 
 
 def enqueue_ops(bufs: _Buffers, iters: int, st, budget: int, blocks: int = 0) -> None:
     """`iters` iterations of a workload's op list on stream `st` (GEMM tiles sized for `budget`
     CUs, 0 = the whole chip)."""
+    # the kinds are looked up once, not per iteration (podrun and --graphs 0 pay this per launch)
+    launches = [(_kind(o)[1], o, t) for o, t in bufs.ops]
     for _ in range(iters):
-        for o, t in bufs.ops:
-            if o.kind == "gemm":
-                a, bt, bias, c = t
-                loadgen.gemm(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
-            elif o.kind == "gemm8":
-                a, bt, bias, c = t
-                loadgen.gemm_fp8(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
-            elif o.kind == "gather":
-                # the indices were generated in range: no check, no sync (this runs under capture)
-                out, table, idx, offsets = t
-                loadgen.embedding_bag(table, idx, offsets, out=out, stream=st, check_indices=False)
-            elif o.kind == "attn":
-                # ctx_lens and the block ids are in range by construction: no check, no sync (capture)
-                out, q, kc, vc, table, ctx = t
-                loadgen.paged_decode_attention(q, kc, vc, table, ctx, out=out, stream=st, check=False)
-            elif o.kind == "triad":
-                x, y, z = t
-                loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
-            else:
-                raise ValueError(f"unknown op kind {o.kind!r}")
+        for launch, o, t in launches:
+            launch(o, t, st, budget, blocks)
 
 
 def lpt_balance(runs: List[PodRun], slot_work: Dict[Tuple[int, int], float], work=None) -> None:

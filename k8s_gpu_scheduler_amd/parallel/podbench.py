@@ -976,6 +976,7 @@ def dump_outputs(path: str, arr: np.ndarray, runs: List[Any], ex: Any, placement
     run reproduces -- units, workload id, iterations, SLO (milli-iterations/s), masked -- one
     row per pod.  The pods' buffers are read after the device has drained: each kernel's output
     is a function of the workload's seeded operands alone."""
+    from .executor import op_output
     os.makedirs(path, exist_ok=True)
     written = []
 
@@ -995,7 +996,7 @@ def dump_outputs(path: str, arr: np.ndarray, runs: List[Any], ex: Any, placement
             k = number[r.pod_id]
             bufs = bufs_of(W.get(r.workload), r.first_unit, r.n_units)
             for j, (o, t) in enumerate(bufs.ops):
-                out = (t[3] if o.is_gemm else t[0]).reshape(-1)
+                out = op_output(o, t).reshape(-1)
                 idx = dump_sample(out.numel(), k, j)
                 if idx is not None:
                     out = out[idx.to(out.device)]

@@ -625,7 +625,7 @@ def test_executor_graph_replay_matches_eager():
     """A pod's kernel sequence captured as one HIP graph and replayed on its (CU-masked)
     stream produces the same outputs as eager launches."""
     from k8s_gpu_scheduler_amd.models.workloads import CATALOG
-    from k8s_gpu_scheduler_amd.parallel.executor import DeviceExecutor, PodRun
+    from k8s_gpu_scheduler_amd.parallel.executor import DeviceExecutor, PodRun, op_output
     wl = "onnx_ssd_mobilenet_1024"          # gemm + triad + gemm
     outs = {}
     for graphs in (False, True):
@@ -637,7 +637,7 @@ def test_executor_graph_replay_matches_eager():
         ex.wait_epoch(runs)
         assert all(r.start.elapsed_time(r.end) > 0 for r in runs)
         bufs = ex.buffers(CATALOG[wl], 2, 2)
-        outs[graphs] = [t[3].float().clone() if o.kind == "gemm" else t[0].clone() for o, t in bufs.ops]
+        outs[graphs] = [op_output(o, t).float().clone() for o, t in bufs.ops]      # (the triad's is fp32 already)
         assert (len(ex._graphs) == 2) == graphs
         ex.close()
     for a, b in zip(outs[False], outs[True]):

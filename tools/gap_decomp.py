@@ -49,7 +49,7 @@ import torch  # noqa: E402
 from k8s_gpu_scheduler_amd.models import workloads as W  # noqa: E402
 from k8s_gpu_scheduler_amd.ops import loadgen  # noqa: E402
 from k8s_gpu_scheduler_amd.ops.cumask import MaskedStream  # noqa: E402
-from k8s_gpu_scheduler_amd.parallel.executor import DeviceExecutor, PodRun  # noqa: E402
+from k8s_gpu_scheduler_amd.parallel.executor import DeviceExecutor, PodRun, enqueue_op  # noqa: E402
 from k8s_gpu_scheduler_amd.parallel.podbench import build_parser, gpu_executor  # noqa: E402
 from k8s_gpu_scheduler_amd.plugins.gpu.devices import CUS_PER_XCD as CUS_PER_UNIT, cu_slice_mask  # noqa: E402
 
@@ -63,19 +63,7 @@ class KindExecutor(DeviceExecutor):
             for o, t in bufs.ops:
                 if self.kind == "gemm" and not o.is_gemm or self.kind == "triad" and o.is_gemm:
                     continue
-                _one(o, t, st, budget, self.triad_blocks)
-
-
-def _one(o, t, st, budget: int, blocks: int = 0) -> None:
-    if o.kind == "gemm":
-        a, bt, bias, c = t
-        loadgen.gemm(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
-    elif o.kind == "gemm8":
-        a, bt, bias, c = t
-        loadgen.gemm_fp8(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
-    else:
-        x, y, z = t
-        loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
+                enqueue_op(o, t, st, budget, self.triad_blocks)
 
 
 def timed(fn: Callable[[], None]) -> float:
@@ -180,7 +168,7 @@ def main() -> None:
                     for o, t in bufs.ops:
                         if kind == "gemm" and not o.is_gemm or kind == "triad" and o.is_gemm:
                             continue
-                        _one(o, t, s_main, n * CUS_PER_UNIT if share else 0)
+                        enqueue_op(o, t, s_main, n * CUS_PER_UNIT if share else 0)
         return f
 
     def split(share: bool, tri_st=None, gemm_st=None, gemm_budget: int = 0) -> Callable[[], None]:
@@ -192,7 +180,7 @@ def main() -> None:
                 b = n * CUS_PER_UNIT if share else gemm_budget
                 for _ in range(it):
                     for o, t in bufs.ops:
-                        _one(o, t, gs if o.is_gemm else ts, b)
+                        enqueue_op(o, t, gs if o.is_gemm else ts, b)
         return f
 
     regimes: Dict[str, Callable[[], None]] = {} if not core else {
