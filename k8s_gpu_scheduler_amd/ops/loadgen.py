@@ -11,8 +11,9 @@ have no bounds checks by design).  On a GPU box the native module is mandatory: 
 path here (tests compare against torch fp32 / fp64 references instead).
 
 Operands may be views into larger allocations (row slices, column slices, padded rows).  The
-host checks enforce, and tests/test_gpu_kernels_exact.py, test_gpu_gather_exact.py and
-test_gpu_decode_attn_exact.py rely on:
+host checks enforce, and tests/test_gpu_kernels_exact.py, test_gpu_gather_exact.py,
+test_gpu_decode_attn_exact.py and test_gpu_corun_exact.py (the same inputs beside another stream's
+kernels) rely on:
 
   * A, Bt: K-contiguous rows, the first element 16-byte aligned, the leading dimension (row
     stride in elements) >= K and a multiple of 8 for bf16, of 16 for fp8 -- every row then
@@ -248,7 +249,10 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torc
         B, P = idx.shape
         if B * P >= 2 ** 31:
             raise ValueError("embedding_bag: more than 2^31 - 1 indices")
-        offsets = torch.arange(B + 1, dtype=torch.int32, device=idx.device) * P
+        # made on the launch stream: the kernel that reads them, and the allocator's reuse of their
+        # memory after this call, are then ordered with it
+        with _launch_stream(stream, idx.device):
+            offsets = torch.arange(B + 1, dtype=torch.int32, device=idx.device) * P
         idx = idx.reshape(-1)
     elif idx.dim() == 1:
         if offsets is None:

@@ -72,7 +72,9 @@ def test_gemm_256_8phase_numerics_and_race_screen(tile):
     counts (the buffer parity flips) to long loops, several grid sizes, each shape run
     repeatedly -- a mis-counted vmcnt or a restage too early shows up as rare wrong tiles
     (guide §5 'A sync-structure edit makes a NEW template'), so every run is checked against
-    an fp32 reference, and A = I with an asymmetric B pins the C layout."""
+    an fp32 reference, and A = I with an asymmetric B pins the C layout.  This screen runs alone on
+    an idle chip, with a tolerance; test_gpu_corun_exact.py runs the same tiles bit-exact while
+    another stream's kernels share their CUs, L2 and HBM."""
     from k8s_gpu_scheduler_amd import _native
     from k8s_gpu_scheduler_amd.ops import loadgen
     h = _native.hip()
