@@ -26,7 +26,6 @@ void gemm_bf16_nt(uintptr_t a, uintptr_t bt, uintptr_t c, uintptr_t bias, int M,
                   size_t workspace_floats = 0);
 int pick_split_k(int M, int N, int K, int cu_budget);
 size_t splitk_workspace_floats(int M, int N, int K, int cu_budget);
-void set_split_k(int s);
 void gemm_fp8_nt(uintptr_t a, uintptr_t bt, uintptr_t c, uintptr_t bias, int M, int N, int K, int lda, int ldb,
                  int ldc, bool relu, uintptr_t stream, int cu_budget);
 void stream_triad(uintptr_t a, uintptr_t b, uintptr_t c, float s, size_t n_floats, int blocks, uintptr_t stream);
@@ -44,18 +43,40 @@ void paged_decode_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintpt
                        float scale, uintptr_t stream);
 // workgroups of that launch: one per (sequence, KV head)
 int paged_decode_workgroups(int S, int Hkv);
-void set_triad_variant(int v);
-void set_gemm_tile(int t);
-void set_w4_probe(int mask);
-void set_w4_prio(int on);
-void set_gemm_policy(int p);
-void set_wide_epilogue(int on);
-void set_xcd_blocks(int on);
-void set_lone_plain_order(int on);
-void set_xcd_group(int rows);
+// The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
+// row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
+// takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where
+// they are read (gemm.hip, triad.hip).
+#define GS_KNOBS(X)                    \
+  X(gemm_tile, 0, 16, 0, RANGE)        \
+  X(gemm_policy, 0, 13, 10, RANGE)     \
+  X(split_k, -1, 8, 0, RANGE)          \
+  X(w4_probe, 0, 3, 0, RANGE)          \
+  X(w4_prio, 0, 1, 0, ON_OFF)          \
+  X(wide_epilogue, 0, 1, 1, ON_OFF)    \
+  X(xcd_blocks, 0, 1, 1, ON_OFF)       \
+  X(lone_plain_order, 0, 1, 1, ON_OFF) \
+  X(xcd_group, 1, 64, 4, RANGE)        \
+  X(triad_variant, 0, 10, 6, RANGE)
+#define GS_KNOB_ID(name, lo, hi, def, kind) k_##name,
+enum Knob { GS_KNOBS(GS_KNOB_ID) kNumKnobs };
+enum KnobKind { RANGE, ON_OFF };
+struct KnobInfo { const char* name; int min, max, def; KnobKind kind; };
+extern const KnobInfo kKnobs[kNumKnobs];
+extern int g_knob[kNumKnobs];
+inline int knob(Knob k) { return g_knob[k]; }
+void set_knob(Knob k, int value);
+void reset_knobs();
 void xcd_probe(uintptr_t out, int blocks, uintptr_t stream);
 int pick_xcd_map(int tiles_m, int tiles_n);
 int pick_gemm_tile(int M, int N, int cu_budget);
+// What gemm_bf16_nt launches for a call, decided on the host alone: the launches in order (a policy-9 GEMM is
+// several row slices [m0, m0 + m), a split-K GEMM the sliced kernel then splitk_reduce as tile 0) and the
+// split factor.  wide_ok: the wide epilogue may run (the wide_epilogue knob is on and C rows are 16-byte
+// aligned); workspace: the caller passes a split-K workspace.
+struct GemmLaunch { int tile; const void* kernel; int grid, block, xmap, m0, m; };
+struct GemmPlan { int split = 1; std::vector<GemmLaunch> launches; };
+GemmPlan plan_gemm(int M, int N, int K, int cu_budget, bool relu, bool bias, bool wide_ok, bool workspace);
 // workgroups of the GEMM launch this shape / CU budget gets (the kernel's CU footprint)
 int gemm_workgroups(int M, int N, int K, int cu_budget, bool fp8, bool split_workspace);
 std::vector<int> peer_access_matrix();

@@ -5,7 +5,11 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cxxabi.h>
+#include <dlfcn.h>
+
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -55,7 +59,6 @@ PYBIND11_MODULE(_hip, m) {
   m.def("pick_split_k", &gs::pick_split_k, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("cu_budget") = 0);
   m.def("splitk_workspace_floats", &gs::splitk_workspace_floats, py::arg("M"), py::arg("N"), py::arg("K"),
         py::arg("cu_budget") = 0);
-  m.def("set_split_k", &gs::set_split_k, py::arg("s"));
   m.def("gemm_fp8_nt", &gs::gemm_fp8_nt, py::arg("a"), py::arg("bt"), py::arg("c"), py::arg("bias"), py::arg("M"),
         py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"), py::arg("relu"),
         py::arg("stream"), py::arg("cu_budget") = 0, py::call_guard<py::gil_scoped_release>());
@@ -70,15 +73,35 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("ld_q"), py::arg("ld_out"), py::arg("ld_table"), py::arg("scale"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
   m.def("paged_decode_workgroups", &gs::paged_decode_workgroups, py::arg("S"), py::arg("Hkv"));
-  m.def("set_triad_variant", &gs::set_triad_variant, py::arg("variant"));
-  m.def("set_gemm_tile", &gs::set_gemm_tile, py::arg("tile"));
-  m.def("set_w4_probe", &gs::set_w4_probe, py::arg("mask"));
-  m.def("set_w4_prio", &gs::set_w4_prio, py::arg("on"));
-  m.def("set_gemm_policy", &gs::set_gemm_policy, py::arg("policy"));
-  m.def("set_wide_epilogue", &gs::set_wide_epilogue, py::arg("on"));
-  m.def("set_xcd_blocks", &gs::set_xcd_blocks, py::arg("on"));
-  m.def("set_lone_plain_order", &gs::set_lone_plain_order, py::arg("on"));
-  m.def("set_xcd_group", &gs::set_xcd_group, py::arg("rows"));
+  // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once
+  for (int k = 0; k < gs::kNumKnobs; ++k)
+    m.def(("set_" + std::string(gs::kKnobs[k].name)).c_str(), [k](int value) { gs::set_knob(gs::Knob(k), value); });
+  auto knob_dict = [](bool defaults) {
+    py::dict out;
+    for (int k = 0; k < gs::kNumKnobs; ++k) out[gs::kKnobs[k].name] = defaults ? gs::kKnobs[k].def : gs::knob(gs::Knob(k));
+    return out;
+  };
+  m.def("knobs", [=]() { return knob_dict(false); });
+  m.def("knob_defaults", [=]() { return knob_dict(true); });
+  m.def("reset_knobs", &gs::reset_knobs);
+  // what gemm_bf16_nt would launch (no GPU needed): the kernels by their demangled names, which the kernel
+  // handles carry as dynamic symbols of this module; c_wide_ok = C rows are 16-byte aligned
+  m.def("gemm_plan", [](int M, int N, int K, int cu_budget, bool relu, bool bias, bool c_wide_ok, bool workspace) {
+    const gs::GemmPlan p = gs::plan_gemm(M, N, K, cu_budget, relu, bias, c_wide_ok && gs::knob(gs::k_wide_epilogue),
+                                         workspace);
+    py::list launches;
+    for (const gs::GemmLaunch& l : p.launches) {
+      Dl_info sym{};
+      dladdr(l.kernel, &sym);
+      char* name = sym.dli_sname ? abi::__cxa_demangle(sym.dli_sname, nullptr, nullptr, nullptr) : nullptr;
+      launches.append(py::dict(py::arg("tile") = l.tile, py::arg("kernel") = std::string(name ? name : ""),
+                               py::arg("grid") = l.grid, py::arg("block") = l.block, py::arg("xmap") = l.xmap,
+                               py::arg("m0") = l.m0, py::arg("m") = l.m));
+      std::free(name);
+    }
+    return py::dict(py::arg("split") = p.split, py::arg("launches") = launches);
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("cu_budget") = 0, py::arg("relu") = false,
+        py::arg("bias") = false, py::arg("c_wide_ok") = true, py::arg("workspace") = false);
   m.def("xcd_probe", &gs::xcd_probe, py::arg("out"), py::arg("blocks"), py::arg("stream"));
   m.def("pick_xcd_map", &gs::pick_xcd_map, py::arg("tiles_m"), py::arg("tiles_n"));
   m.def("pick_gemm_tile", &gs::pick_gemm_tile, py::arg("M"), py::arg("N"), py::arg("cu_budget") = 0);

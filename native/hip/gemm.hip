@@ -20,15 +20,16 @@
 //  * stream_triad (native/hip/triad.hip) -- the HBM-bound pod phase.
 //
 // The one translation unit with GEMM kernels: they live in gemm_tiles.h, gemm_8ph.h and gemm_w4.h
-// (over gemm_device.h); here are the knobs, the tile table and picker, and the launchers.
+// (over gemm_device.h); here are the knobs, the tile table and picker, the planner (plan_gemm) and the
+// one launcher that runs its plan.
 //
-// Launch settings (set_gemm_policy, set_gemm_tile, set_split_k, set_wide_epilogue,
-// set_xcd_blocks, set_xcd_group, set_triad_variant) are process-wide values read on the launching host thread when a kernel is
-// enqueued (a captured HIP graph keeps the values of its capture).  One host thread per rank
+// Launch settings (the knob table GS_KNOBS of api.h, values in knobs.cpp) are process-wide values read on the launching host
+// thread when a kernel is enqueued (a captured HIP graph keeps the values of its capture).  One host thread per rank
 // launches every pod kernel (parallel.executor), so they are plain statics; the defaults are
 // the measured winners; every selectable variant computes the same result (GPU-tested against
 // fp32 PyTorch), the rest of the A/B record lives in profiles/.
 #include <algorithm>
+#include <array>
 #include <type_traits>
 
 #include "api.h"
@@ -73,25 +74,15 @@ void xcd_probe(uintptr_t out, int blocks, uintptr_t stream) {
   HIP_CHECK(hipGetLastError());
 }
 
-// XCD-block tile order (tile_coords): 1 = on (px chosen per grid), 0 = the GROUP_M order over
-// the whole grid (A/B knob).
-static int g_xcd_blocks = 1;
-static int g_xcd_group = 4;         // tile rows per group inside an XCD block
-void set_xcd_blocks(int on) { g_xcd_blocks = on ? 1 : 0; }
-// lone 8-phase GEMMs (whole-chip budget) in the plain GROUP_M order (1, default) or the same
-// order as co-running pods (0, A/B knob)
-static int g_lone_plain_order = 1;
-void set_lone_plain_order(int on) { g_lone_plain_order = on ? 1 : 0; }
-
-void set_xcd_group(int rows) {
-  if (rows < 1 || rows > 64) throw std::runtime_error("xcd group rows must be 1..64");
-  g_xcd_group = rows;
-}
-
+// xcd_blocks: the XCD-block tile order (tile_coords): 1 = on (px chosen per grid), 0 = the GROUP_M order
+// over the whole grid (A/B knob).  xcd_group: tile rows per group inside an XCD block.
+// lone_plain_order: lone 8-phase / 4-wave GEMMs (whole-chip budget) in the plain GROUP_M order (1, default)
+// or the same order as co-running pods (0, A/B knob).
+//
 // px (XCD-block rows, 8 / px columns) minimising the strips one XCD fetches, A rows + B
 // columns of its block, among the splits that divide the grid; 0 = none (legacy order).
 int pick_xcd_map(int tiles_m, int tiles_n) {
-  if (!g_xcd_blocks || (tiles_m * tiles_n) % kXcds) return 0;
+  if (!knob(k_xcd_blocks) || (tiles_m * tiles_n) % kXcds) return 0;
   int best = 0, best_cost = 1 << 30;
   for (int px = 1; px <= kXcds; px *= 2) {
     const int py = kXcds / px;
@@ -99,23 +90,18 @@ int pick_xcd_map(int tiles_m, int tiles_n) {
     const int cost = tiles_m / px + tiles_n / py;
     if (cost < best_cost) best = px, best_cost = cost;
   }
-  return best ? best | (g_xcd_group << 8) : 0;
+  return best ? best | (knob(k_xcd_group) << 8) : 0;
 }
 
-// Wide (LDS-staged, 16-B row stores) epilogue whenever C rows are 16-B aligned; g_wide_epi = 0
+// Wide (LDS-staged, 16-B row stores) epilogue whenever C rows are 16-B aligned; wide_epilogue = 0
 // keeps the scattered 8-B epilogue (A/B knob).
-static int g_wide_epi = 1;
-
-void set_wide_epilogue(int on) { g_wide_epi = on ? 1 : 0; }
-
 static bool wide_ok(const __bf16* Cp, int ldc) {
-  return g_wide_epi && ldc % 8 == 0 && reinterpret_cast<uintptr_t>(Cp) % 16 == 0;
+  return knob(k_wide_epilogue) && ldc % 8 == 0 && reinterpret_cast<uintptr_t>(Cp) % 16 == 0;
 }
 
-// 0 = auto (pick_gemm_tile), 1..16 = that row of kTiles for every GEMM (A/B knob)
-static int g_gemm_tile = 0;
-
-// Tile policy.  Lone GEMMs that still get one block per CU use the 8-phase 256x256 with the
+// gemm_tile: 0 = auto (pick_gemm_tile), 1..16 = that row of kTiles for every GEMM (A/B knob).
+//
+// gemm_policy.  Lone GEMMs that still get one block per CU use the 8-phase 256x256 with the
 // peeled steady-state loop (tile 10; tile 9 4096^3 1306 vs 1109 TF for tile 4, 8192^3 1434 vs
 // 1211, profiles/r01_gemm_big.json; peeling: +5-6 % over tile 9 on every shape,
 // profiles/r02_gemm_big_peeled.json).  1 = default: co-running pods whose CU share the 256x256
@@ -127,64 +113,94 @@ static int g_gemm_tile = 0;
 // Default 10 since round 6: arm 1's tiles, except co-running GEMMs the 256x256 tile fills run the
 // 4-wave kernel (tile 14) -- 606.3 vs 596.4 pods/s, SLOs 61.8 vs 59.0 % over 5 interleaved bench
 // rounds on MI355X (600.6 vs 587.1 over 3 on another box; profiles/r06_w4corun/).
-static int g_gemm_policy = 10;
-// split-K for lone GEMMs whose 256x256 tiles leave CUs idle: -1 = auto (up to 8 slices), 0 = off,
+//
+// split_k: split-K for lone GEMMs whose 256x256 tiles leave CUs idle: -1 = auto (up to 8 slices), 0 = off,
 // 2..8 = at most that many slices.  Off by default: on the tall-K 2048x4096x8192 the split
 // kernel itself runs at ~1540 TF, but the fp32 partials + reduce pass (~144 MB of traffic) put
 // the whole GEMM at 1162 TF vs 1210 for the 128x128 tile and 1290 for hipBLASLt
 // (profiles/r02_gemm_big_splitk.json); a fused last-arriver fixup would need cross-XCD L2
 // coherence for the partials.
-static int g_split_k = 0;
+//
+// w4_prio, w4_probe: tile 14 with whole-kernel priority, and its timing probes (plan_gemm).
 
-void set_gemm_policy(int p) {
-  if (p < 0 || p > 13) throw std::runtime_error("gemm policy must be 0..13");
-  g_gemm_policy = p;
+// The (relu, bias, wide) instantiations of one kernel, at index relu * 4 + bias * 2 + wide.  ACT_KERNELS(k<...>)
+// names the kernel once, with R, B and W where its template takes the three flags.
+using ActKernels = std::array<const void*, 8>;
+template <class F>
+static ActKernels act_kernels(F k) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  return {k(N{}, N{}, N{}), k(N{}, N{}, Y{}), k(N{}, Y{}, N{}), k(N{}, Y{}, Y{}),
+          k(Y{}, N{}, N{}), k(Y{}, N{}, Y{}), k(Y{}, Y{}, N{}), k(Y{}, Y{}, Y{})};
 }
+#define ACT_KERNELS(...)                                                                            \
+  act_kernels([](auto r, auto b, auto w) {                                                          \
+    constexpr bool R = decltype(r)::value, B = decltype(b)::value, W = decltype(w)::value;          \
+    return (void)W, reinterpret_cast<const void*>(&__VA_ARGS__);                                    \
+  })
 
-static int g_w4_probe = 0;
-static int g_w4_prio = 0;
-
-void set_w4_prio(int on) { g_w4_prio = on ? 1 : 0; }
-void set_w4_probe(int mask) {
-  if (mask < 0 || mask > 3) throw std::runtime_error("w4 probe must be 0..3");
-  g_w4_probe = mask;
-}
-
-void set_gemm_tile(int t) {
-  if (t < 0 || t > 16) throw std::runtime_error("gemm tile must be 0..16");
-  g_gemm_tile = t;
-}
-
-void set_split_k(int s) {
-  if (s < -1 || s > 8) throw std::runtime_error("split_k must be 0 (off) .. 8, or -1 (auto)");
-  g_split_k = s == 1 ? 0 : s;
-}
-
-// The tile table: block tile, and the tile that runs instead when the kernel's own limits
-// rule it out (0 = no such limit): small_k_fallback below two K-tiles (K < 128: the 8-phase and
-// 4-wave prologues stage two), narrow_c_fallback when C rows are not 16-B aligned (the 4-wave
-// kernel has only the wide epilogue).  Any tile that does not divide the shape falls back to 3.
+// The tile table, the whole description of a tile: block tile, threads per block, the tile that runs
+// instead when the kernel's own limits rule it out (0 = no such limit): small_k_fallback below two K-tiles
+// (K < 128: the 8-phase and 4-wave prologues stage two), narrow_c_fallback when C rows are not 16-B aligned
+// and the tile has only the wide epilogue; the epilogues it has; whether a lone GEMM takes the plain tile
+// order (plan_gemm); its kernels.  Any tile that does not divide the shape falls back to 3.
 // models/workloads.py keeps a HIP-free copy of the rows the default policy uses.
-struct TileInfo { int bm, bn; int small_k_fallback; int narrow_c_fallback; };
-static const TileInfo kTiles[17] = {
-    {0, 0, 0, 0},        //  0 = auto
-    {128, 128, 0, 0},    //  1: 4 waves, 2 stages, 2 / CU, hoisted reads -- the small-GEMM winner (below)
-    {64, 128, 0, 0},     //  2: 4 waves, 2 / CU, per-k-step reads (hoisting is mixed here)
-    {64, 64, 0, 0},      //  3: 4 waves, 2 / CU, hoisted; always divides (the callers check % 64)
-    {256, 256, 0, 0},    //  4: 8 waves of 128x64, 1 / CU, hoisted
-    {256, 128, 0, 0},    //  5: 8 waves of 64x64, 1 / CU
-    {128, 128, 0, 0},    //  6: tile 1 without hoisted reads (A/B reference)
-    {64, 128, 0, 0},     //  7: tile 2 with 3 stages (2 / CU)
-    {256, 128, 0, 0},    //  8: tile 5 with 3 stages
-    {256, 256, 4, 0},    //  9: 8-phase (gemm_bf16_nt_256_8ph), the original loop
-    {256, 256, 4, 0},    // 10: 8-phase, steady-state K loop peeled (constant vmcnt) + wide epilogue
-    {128, 128, 0, 0},    // 11: tile 1 with 3 LDS stages (counted vmcnt, glds issued 2 K-tiles ahead), 1 / CU
-    {128, 128, 0, 0},    // 12: tile 1 with 4 LDS stages (3 K-tiles ahead), 1 / CU
-    {256, 128, 5, 0},    // 13: 8-phase on 256x128 (<..., BN = 128>, peeled + wide epilogue)
-    {256, 256, 4, 10},   // 14: 4 waves of 128x128 (gemm_bf16_nt_256_w4l); the co-run default (policy 10)
-    {256, 128, 5, 13},   // 15: the same kernel, wave tile 128x64 (policy 11)
-    {128, 128, 1, 1},    // 16: the same kernel, wave tile 64x64, 80 KiB ring, 2 / CU (policy 13)
+enum Epilogues { NARROW, BOTH, WIDE };
+struct TileInfo {
+  int bm, bn, threads, small_k_fallback, narrow_c_fallback;
+  Epilogues epi;
+  bool lone_plain;
+  ActKernels kernel;
 };
+// gemm_bf16_nt_kernel<BM, BN, WGM, WGN, OCC, R, B, STAGES, KT, HOIST, W>, gemm_bf16_nt_256_8ph<R, B, PEEL, W, SPLIT, BN>,
+// gemm_bf16_nt_256_w4l<R, B, PROBE, PRIO, BN, BM>
+static const TileInfo kTiles[17] = {
+    {},  //  0 = auto
+    //  1: 4 waves, 2 stages, 2 / CU, hoisted reads -- the small-GEMM winner (below)
+    {128, 128, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<128, 128, 2, 2, 2, R, B, 2, 64, true, W>)},
+    //  2: 4 waves, 2 / CU, per-k-step reads (hoisting is mixed here)
+    {64, 128, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<64, 128, 2, 2, 2, R, B, 2, BK, false, W>)},
+    //  3: 4 waves, 2 / CU, hoisted; always divides (the callers check % 64)
+    {64, 64, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<64, 64, 2, 2, 2, R, B, 2, 64, true, W>)},
+    //  4: 8 waves of 128x64, 1 / CU, hoisted
+    {256, 256, 512, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<256, 256, 2, 4, 1, R, B, 2, 64, true, W>)},
+    //  5: 8 waves of 64x64, 1 / CU
+    {256, 128, 512, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<256, 128, 4, 2, 1, R, B, 2, BK, false, W>)},
+    //  6: tile 1 without hoisted reads (A/B reference)
+    {128, 128, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<128, 128, 2, 2, 2, R, B, 2, BK, false, W>)},
+    //  7: tile 2 with 3 stages (2 / CU)
+    {64, 128, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<64, 128, 2, 2, 2, R, B, 3, BK, false, W>)},
+    //  8: tile 5 with 3 stages
+    {256, 128, 512, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<256, 128, 4, 2, 1, R, B, 3, BK, false, W>)},
+    //  9: 8-phase (gemm_bf16_nt_256_8ph), the original loop; the 8-B epilogue only
+    {256, 256, 512, 4, 0, NARROW, true, ACT_KERNELS(gemm_bf16_nt_256_8ph<R, B, false, W, false, 256>)},
+    // 10: 8-phase, steady-state K loop peeled (constant vmcnt) + wide LDS-staged epilogue
+    {256, 256, 512, 4, 0, BOTH, true, ACT_KERNELS(gemm_bf16_nt_256_8ph<R, B, true, W, false, 256>)},
+    // 11: tile 1 with 3 LDS stages (counted vmcnt, glds issued 2 K-tiles ahead), 1 / CU
+    {128, 128, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<128, 128, 2, 2, 1, R, B, 3, 64, true, W>)},
+    // 12: tile 1 with 4 LDS stages (3 K-tiles ahead), 1 / CU
+    {128, 128, 256, 0, 0, BOTH, false, ACT_KERNELS(gemm_bf16_nt_kernel<128, 128, 2, 2, 1, R, B, 4, 64, true, W>)},
+    // 13: tile 10's schedule on a 256 x 128 block tile
+    {256, 128, 512, 5, 0, BOTH, true, ACT_KERNELS(gemm_bf16_nt_256_8ph<R, B, true, W, false, 128>)},
+    // 14: 4 waves of 128x128 (gemm_bf16_nt_256_w4l); the co-run default (policy 10)
+    {256, 256, 256, 4, 10, WIDE, true, ACT_KERNELS(gemm_bf16_nt_256_w4l<R, B, 0, false, 256, 256>)},
+    // 15: the same kernel, wave tile 128x64 (policy 11)
+    {256, 128, 256, 5, 13, WIDE, true, ACT_KERNELS(gemm_bf16_nt_256_w4l<R, B, 0, false, 128, 256>)},
+    // 16: the same kernel, wave tile 64x64, 80 KiB ring, 2 / CU (policy 13)
+    {128, 128, 256, 1, 1, WIDE, true, ACT_KERNELS(gemm_bf16_nt_256_w4l<R, B, 0, false, 128, 128>)},
+};
+// tile 14's other kernels: whole-kernel priority (w4_prio), and the timing probes w4_probe = 1..3: steady-loop
+// LDS-DMA (1), reads (2) or both (3) dropped
+static const ActKernels kW4Prio = ACT_KERNELS(gemm_bf16_nt_256_w4l<R, B, 0, true, 256, 256>);
+static const void* const kW4Probe[3] = {reinterpret_cast<const void*>(&gemm_bf16_nt_256_w4l<false, false, 1>),
+                                        reinterpret_cast<const void*>(&gemm_bf16_nt_256_w4l<false, false, 2>),
+                                        reinterpret_cast<const void*>(&gemm_bf16_nt_256_w4l<false, false, 3>)};
+// split-K: the 8-phase kernel writing fp32 partials of one K slice, then splitk_reduce<relu, bias>
+static const void* const kSplitK = reinterpret_cast<const void*>(&gemm_bf16_nt_256_8ph<false, false, true, false, true>);
+static const void* const kSplitKReduce[4] = {reinterpret_cast<const void*>(&splitk_reduce<false, false>),
+                                             reinterpret_cast<const void*>(&splitk_reduce<false, true>),
+                                             reinterpret_cast<const void*>(&splitk_reduce<true, false>),
+                                             reinterpret_cast<const void*>(&splitk_reduce<true, true>)};
 // 6-8 (profiles/r01_gemm_tiles.json): correct, but none beats 128x128 / 2 stages / 2 per CU
 // (4096x2048x2048: 697 / 783 / 898 vs 954 TF; co-run mix 659 / 682 / 733 vs 795 TF): the extra
 // stage costs the second resident block, which hid the tile wait just as well.
@@ -215,7 +231,7 @@ static bool fills(int M, int N, int need) {
 }
 
 int pick_gemm_tile(int M, int N, int cu_budget) {
-  if (g_gemm_tile) return g_gemm_tile;
+  if (knob(k_gemm_tile)) return knob(k_gemm_tile);
   // Measured (profiles/r01_gemm_tiles.json): a lone kernel wants >= 2 workgroups per CU of the
   // 64/128-wide tiles (fill beats per-block efficiency) and the 256x256 tile only when it
   // still fills every CU (4096^3: 1172 vs 1089 TF); co-running pods want the largest
@@ -224,7 +240,7 @@ int pick_gemm_tile(int M, int N, int cu_budget) {
   const bool alone = whole_chip(cu_budget);
   const int budget = alone ? kCus : cu_budget;
   const int per_cu = alone ? 2 : 1;
-  const int p = g_gemm_policy;
+  const int p = knob(k_gemm_policy);
   const bool fits256 = fills<256, 256>(M, N, budget);
   if (alone && fits256) return p == 2 ? 4 : 10;
   if (!alone) {                                    // the co-run arms: the ORDER of the rules is the policy
@@ -263,13 +279,13 @@ int pick_gemm_tile(int M, int N, int cu_budget) {
 // S K-slices when its tiles leave CUs idle -- tiles x S <= CUs, every slice >= 1024 deep and a
 // multiple of 64 -- else 1.  Needs an fp32 workspace of S*M*N floats (splitk_workspace_floats).
 int pick_split_k(int M, int N, int K, int cu_budget) {
-  if (g_gemm_tile) return 1;
+  if (knob(k_gemm_tile)) return 1;
   const bool alone = whole_chip(cu_budget);
   // policy 8 (A/B arm): a co-running pod's GEMM with fewer 256 x 256 tiles
   // than CUs in its share runs the 8-phase kernel split S ways along K (S = tiles needed to
   // cover the share, at most 4, every slice >= 512 deep), fp32 partials reduced by
   // splitk_reduce, instead of the 128 x 128 tile
-  if (!alone && g_gemm_policy == 8) {
+  if (!alone && knob(k_gemm_policy) == 8) {
     if (M % 256 || N % 256) return 1;
     const int tiles = (M / 256) * (N / 256);
     if (tiles >= cu_budget) return 1;
@@ -277,12 +293,12 @@ int pick_split_k(int M, int N, int K, int cu_budget) {
     while (S > 1 && (K % (64 * S) != 0 || K / S < 512)) --S;
     return S;
   }
-  if (g_split_k == 0) return 1;
+  if (knob(k_split_k) == 0) return 1;
   if (!alone) return 1;
   if (M % 256 || N % 256) return 1;
   const int tiles = (M / 256) * (N / 256);
   if (tiles * 2 > kCus) return 1;
-  int S = std::min(g_split_k > 0 ? g_split_k : 8, kCus / tiles);
+  int S = std::min(knob(k_split_k) > 0 ? knob(k_split_k) : 8, kCus / tiles);
   while (S > 1 && (K % (64 * S) != 0 || K / S < 1024)) --S;
   return S;
 }
@@ -306,13 +322,61 @@ static bool fp8_tile_128(int M, int N, int cu_budget) {
   return fills<128, 128>(M, N, whole_chip(cu_budget) ? 2 * kCus : cu_budget);
 }
 
+static void check_shape(int M, int N, int K, const char* who) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % 64 || N % 64) throw std::runtime_error(std::string(who) + ": bad shape");
+}
+
+// Every decision of a bf16 GEMM launch, on the host alone.  Order: forced tile or policy, small_k_fallback,
+// tile 3 when the tile does not divide the shape (resolve_gemm_tile), then narrow_c_fallback.
+GemmPlan plan_gemm(int M, int N, int K, int cu_budget, bool relu, bool bias, bool wide_ok, bool workspace) {
+  check_shape(M, N, K, "plan_gemm");
+  const int act = relu * 4 + bias * 2;
+  GemmPlan p;
+  p.split = workspace ? pick_split_k(M, N, K, cu_budget) : 1;
+  if (p.split > 1) {
+    const size_t n4 = (size_t)M * N / 4;
+    p.launches = {{10, kSplitK, (M / 256) * (N / 256) * p.split, 512, 0, 0, M},
+                  {0, kSplitKReduce[act / 2], (int)std::min<size_t>((n4 + 255) / 256, 8192), 256, 0, 0, M}};
+    return p;
+  }
+  int t = resolve_gemm_tile(M, N, K, cu_budget);
+  if (kTiles[t].epi == WIDE && !wide_ok) {
+    if (knob(k_gemm_tile) == t) throw std::runtime_error("gemm tiles 14-16: C rows must be 16-byte aligned");
+    // a policy on an unaligned C (only co-running GEMMs get these tiles unforced, so `lone` is false)
+    t = kTiles[t].narrow_c_fallback;
+  }
+  const TileInfo& ti = kTiles[t];
+  const void* kernel = ti.kernel[act + (ti.epi == WIDE || (ti.epi == BOTH && wide_ok))];
+  if (t == 14 && knob(k_w4_prio)) kernel = kW4Prio[act + 1];
+  if (t == 14 && knob(k_w4_probe)) kernel = kW4Probe[knob(k_w4_probe) - 1];
+  // a lone GEMM (the whole chip) takes the plain GROUP_M order: 0.936 vs 0.913 of hipBLASLt at
+  // 4096^3, 0.94 vs 0.916 at 4096x8192x4096, 0.935 vs 0.918 at 8192^2x2048, 0.914 vs 0.92 at 8192^3
+  // (7 interleaved rounds, profiles/r04_gemm_xcd/); co-running pods keep the XCD-block order
+  // (+2.6 % bench pods/s, profiles/r02_xcd_block_order_ab.txt)
+  const bool lone = ti.lone_plain && knob(k_lone_plain_order) && whole_chip(cu_budget);
+  // policy 9 (A/B arm, round 6): a co-running pod's 8-phase GEMM with more 256 x 256 tiles than
+  // its CU share runs as back-to-back launches of whole tile rows of at most `cu_budget` tiles
+  // each, so it never holds more CUs than its share and the other pods' stream kernels keep
+  // the rest of the chip (profiles/r06_gap/: GEMM time not hidden under the streams is the
+  // largest term of the step)
+  int rows = M;
+  if (t == 10 && !whole_chip(cu_budget) && knob(k_gemm_policy) == 9 && (M / 256) * (N / 256) > cu_budget)
+    rows = std::max(1, cu_budget / (N / 256)) * 256;
+  for (int m0 = 0; m0 < M; m0 += rows) {
+    const int m = std::min(rows, M - m0);
+    p.launches.push_back({t, kernel, (m / ti.bm) * (N / ti.bn), ti.threads,
+                          lone ? 0 : pick_xcd_map(m / ti.bm, N / ti.bn), m0, m});
+  }
+  return p;
+}
+
 int gemm_workgroups(int M, int N, int K, int cu_budget, bool fp8, bool split_workspace) {
-  if (M <= 0 || N <= 0 || K <= 0 || M % 64 || N % 64) throw std::runtime_error("gemm_workgroups: bad shape");
+  check_shape(M, N, K, "gemm_workgroups");
   if (fp8) return fp8_tile_128(M, N, cu_budget) ? (M / 128) * (N / 128) : (M / 64) * (N / 64);
-  const int S = split_workspace ? pick_split_k(M, N, K, cu_budget) : 1;
-  if (S > 1) return (M / 256) * (N / 256) * S;
-  const TileInfo& ti = kTiles[resolve_gemm_tile(M, N, K, cu_budget)];
-  return (M / ti.bm) * (N / ti.bn);
+  const GemmPlan p = plan_gemm(M, N, K, cu_budget, false, false, true, split_workspace);
+  int blocks = 0;
+  for (const GemmLaunch& l : p.launches) blocks += l.tile ? l.grid : 0;   // tile 0 = splitk_reduce
+  return blocks;
 }
 
 // relu / bias as compile-time flags: f(std::bool_constant<RELU>{}, std::bool_constant<BIAS>{})
@@ -336,73 +400,16 @@ struct GemmArgsT {
 };
 using GemmArgs = GemmArgsT<__bf16>;
 
-template <int BM, int BN, int WGM, int WGN, int OCC, int STAGES = 2, int KT = BK, bool HOIST = false>
-static void launch_gemm(const GemmArgs& g) {
-  const dim3 grid((g.M / BM) * (g.N / BN)), block(WGM * WGN * 64);
-  const int xmap = pick_xcd_map(g.M / BM, g.N / BN);
-  auto go = [&](auto r, auto b, auto w) {
-    hipLaunchKernelGGL((gemm_bf16_nt_kernel<BM, BN, WGM, WGN, OCC, decltype(r)::value, decltype(b)::value, STAGES, KT,
-                                            HOIST, decltype(w)::value>),
-                       grid, block, 0, g.s, g.A, g.B, g.C, g.bias, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, xmap);
-  };
-  with_act(g.relu, g.bias, [&](auto r, auto b) {
-    if (wide_ok(g.C, g.ldc)) go(r, b, std::true_type{});
-    else go(r, b, std::false_type{});
-  });
-}
-
-// tile 9 = the original 8-phase kernel; 10 = peeled steady-state loop + wide LDS-staged
-// epilogue (when C rows are 16-B aligned, else the 8-B epilogue); 13 = tile 10's schedule on a
-// 256 x 128 block tile
-template <bool PEEL, int BN = 256>
-static void launch_8ph(const GemmArgs& g, bool lone) {
-  const dim3 grid((g.M / 256) * (g.N / BN)), block(512);
-  // a lone GEMM (the whole chip) takes the plain GROUP_M order: 0.936 vs 0.913 of hipBLASLt at
-  // 4096^3, 0.94 vs 0.916 at 4096x8192x4096, 0.935 vs 0.918 at 8192^2x2048, 0.914 vs 0.92 at 8192^3
-  // (7 interleaved rounds, profiles/r04_gemm_xcd/); co-running pods keep the XCD-block order
-  // (+2.6 % bench pods/s, profiles/r02_xcd_block_order_ab.txt)
-  const int xmap = lone ? 0 : pick_xcd_map(g.M / 256, g.N / BN);
-  auto go = [&](auto r, auto b, auto w) {
-    hipLaunchKernelGGL((gemm_bf16_nt_256_8ph<decltype(r)::value, decltype(b)::value, PEEL, decltype(w)::value, false, BN>),
-                       grid, block, 0, g.s, g.A, g.B, g.C, g.bias, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, xmap, nullptr);
-  };
-  with_act(g.relu, g.bias, [&](auto r, auto b) {
-    if (PEEL && wide_ok(g.C, g.ldc)) go(r, b, std::true_type{});
-    else go(r, b, std::false_type{});
-  });
-}
-
-static void launch_splitk(const GemmArgs& g, float* ws, int S) {
-  const dim3 grid((g.M / 256) * (g.N / 256) * S), block(512);
-  hipLaunchKernelGGL((gemm_bf16_nt_256_8ph<false, false, true, false, true>), grid, block, 0, g.s, g.A, g.B, g.C,
-                     g.bias, g.M, g.N, g.K / S, g.lda, g.ldb, g.ldc, 0, ws);
-  const size_t n4 = (size_t)g.M * g.N / 4;
-  const int rblocks = (int)std::min<size_t>((n4 + 255) / 256, 8192);
-  with_act(g.relu, g.bias, [&](auto r, auto b) {
-    hipLaunchKernelGGL((splitk_reduce<decltype(r)::value, decltype(b)::value>), dim3(rblocks), dim3(256), 0, g.s, ws, S,
-                       g.M, g.N, g.bias, g.C, g.ldc);
-  });
-}
-
-// tiles 14-16 (wide epilogue only: the caller has checked wide_ok)
-static void launch_w4(const GemmArgs& g, int t, bool lone) {
-  if ((size_t)256 * std::max(g.lda, g.ldb) * 2 >= ((size_t)1 << 31))
-    throw std::runtime_error("gemm tiles 14-16: a 256-row operand block must span < 2 GiB");
-  const int bm = kTiles[t].bm, bn = kTiles[t].bn;
-  const dim3 grid((g.M / bm) * (g.N / bn)), block(256);
-  const int xmap = lone ? 0 : pick_xcd_map(g.M / bm, g.N / bn);
-  decltype(&gemm_bf16_nt_256_w4l<false, false>) k;
-  with_act(g.relu, g.bias, [&](auto r, auto b) {
-    constexpr bool R = decltype(r)::value, Bi = decltype(b)::value;
-    if (t == 16) k = gemm_bf16_nt_256_w4l<R, Bi, 0, false, 128, 128>;
-    else if (t == 15) k = gemm_bf16_nt_256_w4l<R, Bi, 0, false, 128>;
-    else if (g_w4_prio) k = gemm_bf16_nt_256_w4l<R, Bi, 0, true>;
-    else k = gemm_bf16_nt_256_w4l<R, Bi>;
-  });
-  if (t == 14 && g_w4_probe)   // timing probes: steady-loop LDS-DMA (1), reads (2) or both (3) dropped
-    k = g_w4_probe == 1 ? gemm_bf16_nt_256_w4l<false, false, 1>
-        : g_w4_probe == 2 ? gemm_bf16_nt_256_w4l<false, false, 2> : gemm_bf16_nt_256_w4l<false, false, 3>;
-  hipLaunchKernelGGL(k, grid, block, 0, g.s, g.A, g.B, g.C, g.bias, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, xmap);
+// One planned launch, rows [m0, m0 + m) of the call.  The three kernel families take the same eleven
+// leading arguments; the 8-phase kernel's twelfth, ws, is nullptr outside split-K, and the runtime reads
+// only as many as the kernel declares.
+static void launch_tile(const GemmLaunch& l, GemmArgs g, float* ws = nullptr) {
+  g.A += (size_t)l.m0 * g.lda;
+  g.C += (size_t)l.m0 * g.ldc;
+  g.M = l.m;
+  int xmap = l.xmap;
+  void* args[] = {&g.A, &g.B, &g.C, &g.bias, &g.M, &g.N, &g.K, &g.lda, &g.ldb, &g.ldc, &xmap, &ws};
+  HIP_CHECK(hipLaunchKernel(l.kernel, dim3(l.grid), dim3(l.block), args, 0, g.s));
 }
 
 // Host-side argument checks of both entry points: the kernels have no bounds checks by design.
@@ -424,58 +431,23 @@ void gemm_bf16_nt(uintptr_t a, uintptr_t bt, uintptr_t c, uintptr_t bias, int M,
   check_gemm_args("gemm", a, bt, c, bias, M, N, K, lda, ldb, ldc, BK, 8);
   const GemmArgs g{reinterpret_cast<const __bf16*>(a), reinterpret_cast<const __bf16*>(bt), reinterpret_cast<__bf16*>(c),
                    reinterpret_cast<const float*>(bias), M, N, K, lda, ldb, ldc, relu, reinterpret_cast<hipStream_t>(stream)};
-  const int S = workspace ? pick_split_k(M, N, K, cu_budget) : 1;
-  if (S > 1) {
+  const GemmPlan p = plan_gemm(M, N, K, cu_budget, relu, bias != 0, wide_ok(g.C, ldc), workspace != 0);
+  if (p.split > 1) {   // the K slices' fp32 partials, then their reduction
+    int S = p.split;
     if (workspace_floats < (size_t)S * M * N) throw std::runtime_error("gemm: split-K workspace too small");
     check_align(reinterpret_cast<void*>(workspace), "workspace");
-    launch_splitk(g, reinterpret_cast<float*>(workspace), S);
-    HIP_CHECK(hipGetLastError());
+    float* ws = reinterpret_cast<float*>(workspace);
+    GemmArgs slice = g;
+    slice.K = K / S;
+    launch_tile(p.launches[0], slice, ws);
+    const GemmLaunch& r = p.launches[1];
+    void* args[] = {&ws, &S, &M, &N, &slice.bias, &slice.C, &ldc};
+    HIP_CHECK(hipLaunchKernel(r.kernel, dim3(r.grid), dim3(r.block), args, 0, g.s));
     return;
   }
-  int t = resolve_gemm_tile(M, N, K, cu_budget);
-  if (kTiles[t].narrow_c_fallback && !wide_ok(g.C, ldc)) {
-    if (g_gemm_tile == t) throw std::runtime_error("gemm tiles 14-16: C rows must be 16-byte aligned");
-    // a policy on an unaligned C (only co-running GEMMs get these tiles unforced, so `lone` is false)
-    t = kTiles[t].narrow_c_fallback;
-  }
-  const bool lone = g_lone_plain_order && whole_chip(cu_budget);
-  switch (t) {
-    case 1: launch_gemm<128, 128, 2, 2, 2, 2, 64, true>(g); break;
-    case 2: launch_gemm<64, 128, 2, 2, 2>(g); break;
-    case 4: launch_gemm<256, 256, 2, 4, 1, 2, 64, true>(g); break;
-    case 5: launch_gemm<256, 128, 4, 2, 1>(g); break;
-    case 6: launch_gemm<128, 128, 2, 2, 2>(g); break;
-    case 7: launch_gemm<64, 128, 2, 2, 2, 3>(g); break;
-    case 8: launch_gemm<256, 128, 4, 2, 1, 3>(g); break;
-    case 11: launch_gemm<128, 128, 2, 2, 1, 3, 64, true>(g); break;
-    case 12: launch_gemm<128, 128, 2, 2, 1, 4, 64, true>(g); break;
-    case 9: launch_8ph<false>(g, lone); break;
-    case 10:
-      // policy 9 (A/B arm, round 6): a co-running pod's 8-phase GEMM with more 256 x 256 tiles than
-      // its CU share runs as back-to-back launches of whole tile rows of at most `cu_budget` tiles
-      // each, so it never holds more CUs than its share and the other pods' stream kernels keep
-      // the rest of the chip (profiles/r06_gap/: GEMM time not hidden under the streams is the
-      // largest term of the step)
-      if (!whole_chip(cu_budget) && g_gemm_policy == 9 && (M / 256) * (N / 256) > cu_budget) {
-        const int rows = std::max(1, cu_budget / (N / 256)) * 256;
-        for (int m0 = 0; m0 < M; m0 += rows) {
-          GemmArgs part = g;
-          part.A += (size_t)m0 * lda;
-          part.C += (size_t)m0 * ldc;
-          part.M = std::min(rows, M - m0);
-          launch_8ph<true>(part, false);
-        }
-        break;
-      }
-      launch_8ph<true>(g, lone);
-      break;
-    case 13: launch_8ph<true, 128>(g, lone); break;
-    case 14:
-    case 15:
-    case 16: launch_w4(g, t, lone); break;
-    default: launch_gemm<64, 64, 2, 2, 2, 2, 64, true>(g); break;
-  }
-  HIP_CHECK(hipGetLastError());
+  if (p.launches[0].tile >= 14 && (size_t)256 * std::max(lda, ldb) * 2 >= ((size_t)1 << 31))
+    throw std::runtime_error("gemm tiles 14-16: a 256-row operand block must span < 2 GiB");
+  for (const GemmLaunch& l : p.launches) launch_tile(l, g);
 }
 
 template <int BM, int BN, int WGM, int WGN, int OCC>

@@ -1,6 +1,6 @@
 // stream_triad -- a = b + s*c over float4 (16 B/lane) -- the HBM-bound phase of a synthetic pod
-// (the MFMA-bound phase is native/hip/gemm.hip).  set_triad_variant is a process-wide launch
-// setting read on the launching host thread, like the GEMM knobs.
+// (the MFMA-bound phase is native/hip/gemm.hip).  The triad_variant knob is a process-wide launch
+// setting read on the launching host thread, like the GEMM knobs (api.h, gemm.hip).
 #include "api.h"
 #include "common.h"
 
@@ -65,19 +65,12 @@ __global__ void __launch_bounds__(256) stream_triad_u(float4* __restrict__ a_, c
   }
 }
 
-// 6 = auto: working set (3 arrays) <= 96 MiB -> cached 2x-unrolled loads (the stream
-// stays in the 256 MiB Infinity Cache across iterations: 7.1 TB/s measured), larger ->
+// The triad_variant knob.  6 = auto: working set (3 arrays) <= 96 MiB -> cached 2x-unrolled loads (the
+// stream stays in the 256 MiB Infinity Cache across iterations: 7.1 TB/s measured), larger ->
 // non-temporal 4x (6.5 TB/s vs 6.1 for torch.add) -- profiles/r01_kernel_bench.json.
-static int g_triad_variant = 6;
-
 // 5 = non-temporal 2x (22 VGPRs), 7 = non-temporal 3x (<= 32 VGPRs): a triad wave small enough
 // to fit beside an 8-phase GEMM block's 2 x 240 VGPRs per SIMD (the 4x variant's 38 VGPRs do
 // not, so a CU running a 256 x 256 GEMM block takes no triad wave at all; round 6 A/B)
-void set_triad_variant(int v) {
-  if (v < 0 || v > 10) throw std::runtime_error("triad variant must be 0..10 (6 = auto)");
-  g_triad_variant = v;
-}
-
 void stream_triad(uintptr_t a, uintptr_t b, uintptr_t c, float s, size_t n_floats, int blocks, uintptr_t stream) {
   if (n_floats % 4) throw std::runtime_error("triad: n must be a multiple of 4");
   check_align(reinterpret_cast<void*>(a), "a");
@@ -89,7 +82,7 @@ void stream_triad(uintptr_t a, uintptr_t b, uintptr_t c, float s, size_t n_float
   auto B = reinterpret_cast<const float4*>(b);
   auto Cc = reinterpret_cast<const float4*>(c);
   const size_t n4 = n_floats / 4;
-  int variant = g_triad_variant;
+  int variant = knob(k_triad_variant);
   if (variant == 6) variant = (n_floats * 12 <= (size_t)96 << 20) ? 1 : 3;
   // 9 / 10 (A/B arms): write-through stores only for the largest streams (arrays >= 256 / 128 MiB,
   // where a lone sc1 stream gains most), non-temporal below

@@ -43,11 +43,7 @@ def shapes():
 
 
 def _restore():
-    h.set_gemm_policy(10)
-    h.set_gemm_tile(0)
-    h.set_split_k(0)
-    h.set_xcd_blocks(1)
-    h.set_xcd_group(4)
+    h.reset_knobs()
 
 
 def record():

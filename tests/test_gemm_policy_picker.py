@@ -18,8 +18,7 @@ SMALL = {0: 1, 1: 1, 2: 1, 3: 5, 4: 8, 5: 11, 6: 12, 7: 13, 8: 1, 9: 1, 10: 1, 1
 @pytest.fixture(autouse=True)
 def _restore():
     yield
-    h.set_gemm_policy(10)                                      # the default since round 6
-    h.set_gemm_tile(0)
+    h.reset_knobs()                                            # policy 10 is the default since round 6
 
 
 @pytest.mark.parametrize("policy", sorted(SMALL))

@@ -50,16 +50,13 @@ NEEDS_K128 = (9, 10, 13, 14, 15, 16)
 # 5-slot ring) and one long loop
 TILE_KS = (128, 192, 256, 320, 448, 1088)
 
-KNOB_DEFAULTS = (("gemm_tile", 0), ("gemm_policy", 10), ("split_k", 0), ("triad_variant", 6), ("xcd_group", 4),
-                 ("xcd_blocks", 1), ("wide_epilogue", 1), ("lone_plain_order", 1), ("w4_prio", 0))
-
 
 # ------------------------------------------------------------------------------------------------
 # helpers (CPU-tested in test_kernels_exact_helpers.py)
 # ------------------------------------------------------------------------------------------------
 def restore_knobs(h):
-    for name, value in KNOB_DEFAULTS:
-        getattr(h, "set_" + name)(value)
+    """Every launch knob back at its default (the defaults are pinned in test_gemm_plan_cpu.py)."""
+    h.reset_knobs()
 
 
 @contextlib.contextmanager

@@ -10,6 +10,8 @@ import os
 import pytest
 import torch
 
+from test_gpu_kernels_exact import knobs
+
 pytestmark = pytest.mark.gpu
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
 
@@ -47,8 +49,7 @@ def test_gemm_every_tile_variant(tile):
     from k8s_gpu_scheduler_amd import _native
     from k8s_gpu_scheduler_amd.ops import loadgen
     h = _native.hip()
-    h.set_gemm_tile(tile)
-    try:
+    with knobs(h, gemm_tile=tile):
         for (M, N, K) in [(256, 256, 128), (384, 640, 320), (1024, 1536, 1536), (512, 768, 2048)]:
             a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
             bt = torch.randn(N, K, device="cuda").to(torch.bfloat16)
@@ -56,8 +57,6 @@ def test_gemm_every_tile_variant(tile):
             out = loadgen.gemm(a, bt, bias=b, relu=True)
             ref = torch.relu(a.float() @ bt.float().T + b)
             assert (out.float() - ref).abs().max().item() <= 0.01 * ref.abs().max().item() + 1e-2
-    finally:
-        h.set_gemm_tile(0)
 
 
 @pytest.mark.parametrize("tile", [9, 10, 11, 12, 13, 14, 15, 16])
@@ -78,8 +77,7 @@ def test_gemm_256_8phase_numerics_and_race_screen(tile):
     from k8s_gpu_scheduler_amd import _native
     from k8s_gpu_scheduler_amd.ops import loadgen
     h = _native.hip()
-    h.set_gemm_tile(tile)
-    try:
+    with knobs(h, gemm_tile=tile):
         for (M, N, K) in [(256, 256, 64), (256, 256, 128), (256, 512, 192), (512, 256, 320), (768, 1024, 1024),
                           (512, 512, 384), (2048, 2048, 4096), (4096, 4096, 640), (1024, 512, 1088)]:
             g = torch.Generator(device="cuda").manual_seed(M * 7 + N * 3 + K)
@@ -98,8 +96,6 @@ def test_gemm_256_8phase_numerics_and_race_screen(tile):
         eye = torch.eye(n, device="cuda", dtype=torch.bfloat16)
         asym = (torch.arange(n * n, device="cuda", dtype=torch.float32).reshape(n, n) % 97).to(torch.bfloat16)
         assert torch.equal(loadgen.gemm(eye, asym).float(), asym.float().T)
-    finally:
-        h.set_gemm_tile(0)
 
 
 @pytest.mark.parametrize("M,N,K,relu,bias", [(2048, 4096, 8192, True, True), (1024, 1024, 8192, False, False),
@@ -109,11 +105,8 @@ def test_gemm_split_k_matches_fp32_reference(hip, M, N, K, relu, bias):
     kernel per K slice -> fp32 partials -> reduce + bias + ReLU; repeated runs screen for
     ordering races."""
     from k8s_gpu_scheduler_amd.ops import loadgen
-    hip.set_split_k(-1)
-    try:
+    with knobs(hip, split_k=-1):
         _split_k_case(hip, loadgen, M, N, K, relu, bias)
-    finally:
-        hip.set_split_k(0)
 
 
 def _split_k_case(hip, loadgen, M, N, K, relu, bias):
@@ -140,8 +133,7 @@ def test_gemm_corun_split_k_policy8_matches_fp32_reference(hip, M, N, K, relu, b
     256 x 256 tile per CU, runs split along K on the 8-phase kernel (2-4 slices) -> fp32 partials ->
     reduce; checked against fp32 PyTorch with the race screen's repeated runs."""
     from k8s_gpu_scheduler_amd.ops import loadgen
-    hip.set_gemm_policy(8)
-    try:
+    with knobs(hip, gemm_policy=8):
         assert hip.pick_split_k(M, N, K, 64) > 1
         g = torch.Generator(device="cuda").manual_seed(M + 5 * N + K)
         a = (torch.rand(M, K, device="cuda", generator=g) * 2 - 1).to(torch.bfloat16)
@@ -156,8 +148,6 @@ def test_gemm_corun_split_k_policy8_matches_fp32_reference(hip, M, N, K, relu, b
             out.fill_(float("nan"))
             loadgen.gemm(a, bt, out=out, bias=b, relu=relu, cu_budget=64)
             assert (out.float() - ref).abs().max().item() <= tol
-    finally:
-        hip.set_gemm_policy(10)
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 2560, 2560), (2048, 2560, 1536), (4096, 2048, 1024)])
@@ -166,8 +156,7 @@ def test_gemm_share_capped_policy9_matches_fp32_reference(hip, M, N, K):
     back-to-back launches of whole tile rows (<= 64 tiles each); every row slice lands in the
     right place (fp32 PyTorch reference, repeated runs)."""
     from k8s_gpu_scheduler_amd.ops import loadgen
-    hip.set_gemm_policy(9)
-    try:
+    with knobs(hip, gemm_policy=9):
         assert hip.pick_gemm_tile(M, N, 64) == 10
         g = torch.Generator(device="cuda").manual_seed(M + 7 * N + K)
         a = (torch.rand(M, K, device="cuda", generator=g) * 2 - 1).to(torch.bfloat16)
@@ -180,8 +169,6 @@ def test_gemm_share_capped_policy9_matches_fp32_reference(hip, M, N, K):
             out.fill_(float("nan"))
             loadgen.gemm(a, bt, out=out, bias=b, relu=True, cu_budget=64)
             assert (out.float() - ref).abs().max().item() <= tol
-    finally:
-        hip.set_gemm_policy(10)
 
 
 @pytest.mark.parametrize("policy,small_tile", [(11, 15), (13, 16)])
@@ -189,8 +176,7 @@ def test_gemm_corun_policy11_13_four_wave_matches_fp32_reference(hip, policy, sm
     """Arms 11 / 13: arm 10, plus co-running GEMMs too small for 256 x 256 tiles on the 4-wave
     kernel at 256 x 128 (tile 15) / 128 x 128 (tile 16) -- fp32 PyTorch reference, repeated runs."""
     from k8s_gpu_scheduler_amd.ops import loadgen
-    hip.set_gemm_policy(policy)
-    try:
+    with knobs(hip, gemm_policy=policy):
         for M, N, K, tile in [(1024, 2048, 1024, small_tile), (1024, 2560, 2560, small_tile), (4096, 4096, 512, 14)]:
             assert hip.pick_gemm_tile(M, N, 64) == tile
             g = torch.Generator(device="cuda").manual_seed(M + 3 * N + K)
@@ -204,8 +190,6 @@ def test_gemm_corun_policy11_13_four_wave_matches_fp32_reference(hip, policy, sm
                 out.fill_(float("nan"))
                 loadgen.gemm(a, bt, out=out, bias=b, relu=True, cu_budget=64)
                 assert (out.float() - ref).abs().max().item() <= tol, (M, N, K)
-    finally:
-        hip.set_gemm_policy(10)
 
 
 @pytest.mark.parametrize("prio", [0, 1])
@@ -214,9 +198,7 @@ def test_gemm_corun_policy10_four_wave_matches_fp32_reference(hip, prio):
     kernel (tile 14), in the XCD-block tile order, with and without whole-kernel priority; the
     unaligned-C fallback takes the 8-phase kernel (fp32 PyTorch reference, repeated runs)."""
     from k8s_gpu_scheduler_amd.ops import loadgen
-    hip.set_gemm_policy(10)
-    hip.set_w4_prio(prio)
-    try:
+    with knobs(hip, gemm_policy=10, w4_prio=prio):
         for M, N, K in [(4096, 4096, 1024), (2048, 2560, 2560), (8192, 2048, 192)]:
             assert hip.pick_gemm_tile(M, N, 64) == 14
             g = torch.Generator(device="cuda").manual_seed(M + 5 * N + K + prio)
@@ -238,9 +220,6 @@ def test_gemm_corun_policy10_four_wave_matches_fp32_reference(hip, prio):
         out = wide[:, 4:]
         loadgen.gemm(a, bt, out=out, cu_budget=64)
         torch.testing.assert_close(out.float(), a.float() @ bt.float().T, atol=0.1, rtol=0.02)
-    finally:
-        hip.set_w4_prio(0)
-        hip.set_gemm_policy(10)
 
 
 @pytest.mark.parametrize("slice_", [0, 1])
@@ -249,11 +228,8 @@ def test_gemm_split_k_layout_identity(hip, slice_):
     and each slice's K offset exactly."""
     from k8s_gpu_scheduler_amd.ops import loadgen
     n, K = 256, 2048
-    hip.set_split_k(-1)
-    try:
+    with knobs(hip, split_k=-1):
         _split_k_identity(hip, loadgen, n, K, slice_)
-    finally:
-        hip.set_split_k(0)
 
 
 def _split_k_identity(hip, loadgen, n, K, slice_):
@@ -336,7 +312,7 @@ def test_triad_variants_match_reference():
     n = (1 << 20) + 4 * 123
     b, c = torch.rand(n, device="cuda"), torch.rand(n, device="cuda")
     ref = b + 1.5 * c
-    try:
+    with knobs(h):
         for v in range(11):
             h.set_triad_variant(v)
             a = torch.full_like(b, -1.0)
@@ -344,8 +320,6 @@ def test_triad_variants_match_reference():
             torch.testing.assert_close(a, ref, msg=f"variant {v}")
         with pytest.raises(Exception):
             h.set_triad_variant(11)
-    finally:
-        h.set_triad_variant(6)
 
 
 def test_cu_mask_slices_map_to_all_xccs():
@@ -924,8 +898,7 @@ def test_xcd_dispatch_and_tile_orders_bit_exact():
     bt = ((torch.rand(N, K, device="cuda") * 2 - 1) * 0.05).to(torch.bfloat16)
     bias = torch.randn(N, device="cuda")
     y, z = torch.rand(1 << 20, device="cuda"), torch.rand(1 << 20, device="cuda")
-    try:
-        h.set_gemm_tile(10)
+    with knobs(h, gemm_tile=10):
         # a co-running pod's GEMM (CU budget 64) takes the XCD-block order, a lone one the plain
         # GROUP_M order (set_lone_plain_order); every order computes the same bits
         ref = loadgen.gemm(a, bt, bias=bias, relu=True, cu_budget=64)
@@ -945,7 +918,3 @@ def test_xcd_dispatch_and_tile_orders_bit_exact():
         for bad in (17, 18, -1):                  # (tiles 11-13 exist since round 5, 14-16 since round 6)
             with pytest.raises(Exception):
                 h.set_gemm_tile(bad)
-    finally:
-        h.set_xcd_blocks(1)
-        h.set_lone_plain_order(1)
-        h.set_gemm_tile(0)
