@@ -24,6 +24,10 @@ stream, no MFMA work, and a rate that depends on where the rows sit (L2 > Infini
 A fourth is "attn", decode attention over a paged KV cache (ops.loadgen.paged_decode_attention):
 HBM-bound too, but its traffic is 8 KiB cache slabs named by a block table, its two products run on
 the matrix cores, and it has a softmax (transcendentals, cross-lane reductions) in the loop.
+A fifth kernel character is "prefill", chunked-prefill attention over the same cache
+(ops.loadgen.paged_prefill_attention): many new tokens per sequence attending causally, so every
+cache slab is reused by all of them and the op is MFMA-bound -- but unlike a GEMM's, each of its
+MFMAs sits behind exps, cross-lane maxima and a rescale of the accumulators.
 """
 from __future__ import annotations
 
@@ -31,24 +35,31 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 
-ATTN_HEAD_DIM = 128               # the decode-attention kernel's head dim ...
-ATTN_BLOCK_TOKENS = 32            # ... and KV-cache block size (native/hip/decode_attn.hip)
+ATTN_HEAD_DIM = 128               # the attention kernels' head dim ...
+ATTN_BLOCK_TOKENS = 32            # ... and KV-cache block size (native/hip/decode_attn.hip, prefill_attn.hip)
 
 
 @dataclass(frozen=True)
 class Op:
     kind: str              # "gemm" (bf16) | "gemm8" (fp8 e4m3, bf16 out) | "triad" | "gather" (bf16 embedding bag)
     #                        | "attn" (bf16 paged-KV decode attention, head dim 128, blocks of 32 tokens)
-    M: int = 0             # gather: bags; attn: sequences
-    N: int = 0             # gather: D, the row length; attn: query heads
-    K: int = 0             # gather: pooling factor (rows per bag); attn: context tokens per sequence
+    #                        | "prefill" (bf16 paged-KV chunked-prefill attention over the same cache)
+    M: int = 0             # gather: bags; attn, prefill: sequences
+    N: int = 0             # gather: D, the row length; attn, prefill: query heads
+    K: int = 0             # gather: pooling factor (rows per bag); attn, prefill: context tokens per sequence
     relu: bool = True
     n_floats: int = 0      # triad
-    rows: int = 0          # gather: rows of the table; attn: KV heads
+    rows: int = 0          # gather: rows of the table; attn, prefill: KV heads
+    q: int = 0             # prefill: chunk tokens per sequence (the last q of the K context tokens)
 
     @property
     def is_gemm(self) -> bool:
         return self.kind in ("gemm", "gemm8")
+
+    @property
+    def on_mfma(self) -> bool:
+        """MFMA work in the roofline: costed max(flops term, bytes term), its flops on the MFMA side."""
+        return self.is_gemm or self.kind == "prefill"
 
     @property
     def flops(self) -> float:
@@ -56,6 +67,9 @@ class Op:
             return 1.0 * self.M * self.K * self.N                 # one add per gathered element
         if self.kind == "attn":                                   # q . K^T and P . V, a multiply-add each
             return 4.0 * self.M * self.N * self.K * ATTN_HEAD_DIM
+        if self.kind == "prefill":                                # the same per (query, token at or below it) pair:
+            pairs = self.q * (self.K - self.q) + self.q * (self.q + 1) / 2        # the prefix, then the causal triangle
+            return 4.0 * ATTN_HEAD_DIM * self.M * self.N * pairs
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -69,6 +83,9 @@ class Op:
         if self.kind == "attn":                                   # K and V, q and out, block table, ctx_lens
             return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.N * ATTN_HEAD_DIM
                     + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M)
+        if self.kind == "prefill":                                # K and V read once, q and out, table, ctx_lens, q_start
+            return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.q * self.N * ATTN_HEAD_DIM
+                    + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + 4.0 * (self.M + 1))
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -84,6 +101,8 @@ class Op:
             return default_gather_workgroups(self.M)
         if self.kind == "attn":
             return default_attn_workgroups(self.M, self.rows)
+        if self.kind == "prefill":
+            return default_prefill_workgroups(self.M, self.N, self.rows, self.q)
         return None
 
 
@@ -171,22 +190,38 @@ EXTRA: Dict[str, Workload] = {
 }
 
 
+# Workloads whose op kind the pinned tables of test_op_kinds_cpu.py do not list yet (they move to
+# EXTRA together with those tables):
+#   llm_prefill_2048  one Llama-8B-like decoder layer in the prefill phase: two sequences that each
+#                     append a 1,024-token chunk to 3,072 cached tokens -- the fused QKV projection
+#                     of the 2,048 new tokens (2048 x 6144 x 4096), chunked-prefill attention of 32
+#                     query heads over 8 KV heads with 4,096 tokens of context, the output projection
+#                     (2048 x 4096 x 4096).  The paged KV cache is 32 MiB and stays in the Infinity
+#                     Cache: the attention is MFMA-bound, its 1.2e11 flops level with the two GEMMs'
+#                     1.7e11.  The prefill is a fifth kernel character; no co-run groups are
+#                     measured with it yet
+STAGED: Dict[str, Workload] = {
+    "llm_prefill_2048": Workload("llm_prefill_2048", "llm_prefill", "hip", 2048,
+                                 (Op("gemm", 2048, 6144, 4096), Op("prefill", 2, 32, 4096, rows=8, q=1024),
+                                  Op("gemm", 2048, 4096, 4096)), 0.25),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog or extra workload by exact name."""
-    w = CATALOG.get(name)
-    if w is None:
-        w = EXTRA.get(name)
-    if w is None:
-        raise KeyError(name)
-    return w
+    """A catalog, extra or staged workload by exact name."""
+    for table in (CATALOG, EXTRA, STAGED):
+        w = table.get(name)
+        if w is not None:
+            return w
+    raise KeyError(name)
 
 
 def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
-    the catalog."""
+    the catalog, the staged ones after those."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA):
+    for table in (CATALOG, EXTRA, STAGED):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -201,8 +236,8 @@ def roofline_split(pod_name: str, tflops: float = 1.0e3, tbps: float = 6.0) -> O
         w = workload_for_pod(pod_name)
     except KeyError:
         return None
-    m = sum(o.flops / o.mfma_rate() for o in w.ops if o.is_gemm) / (tflops * 1e12)
-    h = sum(o.bytes for o in w.ops if not o.is_gemm) / (tbps * 1e12)
+    m = sum(o.flops / o.mfma_rate() for o in w.ops if o.on_mfma) / (tflops * 1e12)
+    h = sum(o.bytes for o in w.ops if not o.on_mfma) / (tbps * 1e12)
     return m, h
 
 
@@ -264,12 +299,23 @@ def default_attn_workgroups(S: int, Hkv: int) -> int:
     return S * Hkv
 
 
+PREFILL_COLUMNS = 128              # (chunk token, head of the group) columns per workgroup (native/hip/prefill_attn.hip)
+
+
+def default_prefill_workgroups(S: int, Hq: int, Hkv: int, max_q_len: int) -> int:
+    """Workgroups the native prefill-attention launch gets: one per (sequence, KV head, tile of 128
+    columns), a column being a (chunk token, head of the KV head's group) pair and the tiles counted
+    for max_q_len tokens -- a pure-Python copy of paged_prefill_workgroups
+    (native/hip/prefill_attn.hip), pinned against it in tests/test_prefill_attn_cpu.py."""
+    return S * Hkv * -(-max_q_len * (Hq // Hkv) // PREFILL_COLUMNS)
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
     launches them for `cu_budget` under the default policy (default_gemm_workgroups), gather
     workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups
-    count them, the
+    and default_prefill_workgroups count them, the
     stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
@@ -291,7 +337,7 @@ def roofline_seconds(w: Workload, share: float, peak_tflops: float = 1100.0, hbm
     with measurements."""
     t = 0.0
     for o in w.ops:
-        if o.is_gemm:
+        if o.on_mfma:
             t += max(o.flops / (peak_tflops * o.mfma_rate() * 1e12 * share),
                      o.bytes / (hbm_tbps * 1e12 * share ** share_bw_exp))
         else:

@@ -1,18 +1,21 @@
 """Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
-headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip).
+headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
+native/hip/prefill_attn.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
 `embedding_bag(table, idx, offsets)` gathers indexed table rows and sums them per bag (random-row
 HBM / cache traffic, no MFMA); `paged_decode_attention(q, k_cache, v_cache, block_table, ctx_lens)`
 is LLM decode attention over a paged KV cache (block-table-indexed HBM traffic, MFMA products, a
-softmax in the loop).  Shapes are validated on the host before launch (the kernels
+softmax in the loop); `paged_prefill_attention(q, k_cache, v_cache, block_table, ctx_lens, q_start)`
+is chunked-prefill (append) attention over the same cache: many new tokens per sequence attending
+causally (MFMA-bound, the softmax inside the matrix loop).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
 Operands may be views into larger allocations (row slices, column slices, padded rows).  The
 host checks enforce, and tests/test_gpu_kernels_exact.py, test_gpu_gather_exact.py,
-test_gpu_decode_attn_exact.py and test_gpu_corun_exact.py (the same inputs beside another stream's
+test_gpu_decode_attn_exact.py, test_gpu_prefill_attn_exact.py and test_gpu_corun_exact.py (the same inputs beside another stream's
 kernels) rely on:
 
   * A, Bt: K-contiguous rows, the first element 16-byte aligned, the leading dimension (row
@@ -44,7 +47,21 @@ kernels) rely on:
     trusts ctx_lens and the block ids: check=True verifies 0 <= ctx <= 32 * max_blocks and
     0 <= id < NB for the ceil(ctx / 32) leading entries of each row -- the ones the sequence names;
     the others are never read as block ids -- on the device first (one sync); a caller that passes
-    False guarantees them itself.
+    False guarantees them itself;
+  * paged_prefill_attention: the caches, block_table and ctx_lens as for the decode attention; q and
+    out bf16 [Tq, Hq, 128], packed over the S sequences, with contiguous [Hq, 128] slabs, a token
+    stride >= Hq * 128 and a multiple of 8, the first element 16-byte aligned; q_start int32 [S + 1],
+    contiguous, CSR like the gather's offsets: the chunk of sequence s is rows q_start[s] ..
+    q_start[s + 1] - 1, q_len[s] of them, non-decreasing with q_start[0] >= 0 and q_start[S] <= Tq.
+    ctx_lens[s] counts all tokens of s in the cache, the chunk's own included (a server appends the
+    chunk's K / V before it attends); query i of s has position p = ctx_lens[s] - q_len[s] + i and
+    attends tokens [0, p], causal with the diagonal included.  q_len[s] <= ctx_lens[s];
+    q_len[s] == 0 is legal and writes nothing.  max_q_len bounds every q_len (it sizes the grid;
+    the workgroups past a sequence's chunk exit at once).  The kernel trusts all of it: check=True
+    verifies ctx_lens and the named block ids as above, q_start, q_len <= ctx_lens and
+    q_len <= max_q_len on the device first (one sync, which also computes a max_q_len of None);
+    check=False needs max_q_len and never syncs.  With every q_len == 1 this is the decode
+    attention.
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -52,7 +69,15 @@ written; the gather reads only the D elements of the rows the bags name (and the
 reads q's S x Hq x 128 window, ctx_lens, the named table entries and the (block, KV head) slabs they
 name -- whole slabs, but the slots of a sequence's last block past ctx may hold anything (NaN
 included) without touching the output: their scores are replaced by -inf and their V elements by
-zero -- and writes only out's S x Hq x 128 window.
+zero -- and writes only out's S x Hq x 128 window.  The prefill attention reads the q rows
+[q_start[s], q_start[s + 1]) of each sequence, ctx_lens, q_start, the ceil(ctx / 32) leading table
+entries of each sequence and the (block, KV head) slabs they name, and writes only the out rows
+[q_start[0], q_start[S]).  The slots of a sequence's last block past ctx may again hold anything:
+they lie above every position, so their scores are replaced by -inf with a select, and their V
+elements by zero.  A non-finite K or V value of a token inside ctx follows the NaN rule below for
+that sequence's queries at or after the token; it leaves the outputs of earlier queries of the same
+sequence unspecified (the token's probability is 0 there, but 0 * NaN in the V fragment the columns
+share cannot be kept out per column); it never reaches another sequence or KV head.
 
 Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
 of the conversion and float64 sums):
@@ -80,7 +105,13 @@ of the conversion and float64 sums):
     normaliser is summed from the fp32 probabilities; the probabilities are rounded to bf16 for
     the P . V MFMA (at most 2^-9 relative each), which accumulates in fp32; the partial results
     of the four waves are merged in fp32, divided by the normaliser (an IEEE division) and rounded
-    to bf16 once.  ctx == 0 gives a row of +0.0.
+    to bf16 once.  ctx == 0 gives a row of +0.0;
+  * paged_prefill_attention (pinned by tests/test_gpu_prefill_attn_exact.py): the same contract, so
+    the decode attention's error derivation carries over -- fp32 q . k on the MFMA, scale on the
+    fp32 score, the online softmax in fp32 with exp(x) = 2^(x * log2 e), the normaliser summed from
+    the fp32 probabilities, the probabilities rounded to bf16 only as the P . V operand, O in fp32,
+    one IEEE division by the normaliser and one bf16 rounding.  A column's running state lives in
+    one wave for the whole walk: there is no merge of partial results.
 """
 from __future__ import annotations
 
@@ -298,6 +329,82 @@ def embedding_bag(table: torch.Tensor, idx: torch.Tensor, offsets: Optional[torc
 ATTN_GROUPS = (1, 2, 4, 8, 16)          # query heads per KV head (the MFMA's 16 columns hold a group)
 
 
+def _paged_attn_operands(name: str, rows: str, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                         block_table: torch.Tensor, ctx_lens: torch.Tensor, out: Optional[torch.Tensor],
+                         q_start: Optional[torch.Tensor] = None):
+    """The host checks the two paged attentions share: dtypes, ranks, the fixed head dim and block
+    size, the head ratio, the cache layout, the table and ctx_lens against the S sequences, the output
+    (made when None) and the strides and alignment of q and out.  `rows` names what q's first
+    dimension counts: "sequence" (decode: S is that dimension) or "token" (prefill: S is
+    q_start's length less one).  Returns (S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table)."""
+    if q.dtype != torch.bfloat16 or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 q, k_cache and v_cache")
+    if block_table.dtype != torch.int32 or ctx_lens.dtype != torch.int32:
+        raise TypeError(f"{name} expects an int32 block_table and ctx_lens")
+    if q_start is not None and q_start.dtype != torch.int32:
+        raise TypeError(f"{name} expects an int32 q_start")
+    first = "S" if q_start is None else "Tq"
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 or block_table.dim() != 2 or ctx_lens.dim() != 1:
+        raise ValueError(f"{name} expects q [{first}, Hq, 128], k_cache [NB, Hkv, 32, 128], "
+                         "v_cache [NB, Hkv, 128, 32], block_table [S, max_blocks] and ctx_lens [S]")
+    if q_start is not None and (q_start.dim() != 1 or q_start.numel() < 1):
+        raise ValueError(f"{name}: q_start must be 1-D of length S + 1")
+    R, Hq, D = q.shape
+    S, of = (R, "q") if q_start is None else (q_start.numel() - 1, "q_start")
+    NB, Hkv, T, Dk = k_cache.shape
+    if D != ATTN_HEAD_DIM or Dk != ATTN_HEAD_DIM or v_cache.shape[2] != ATTN_HEAD_DIM:
+        raise ValueError(f"{name}: the head dim must be {ATTN_HEAD_DIM}")
+    if T != ATTN_BLOCK_TOKENS or v_cache.shape[3] != ATTN_BLOCK_TOKENS:
+        raise ValueError(f"{name}: the cache block size must be {ATTN_BLOCK_TOKENS} tokens")
+    if tuple(v_cache.shape) != (NB, Hkv, ATTN_HEAD_DIM, ATTN_BLOCK_TOKENS):
+        raise ValueError(f"{name}: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} "
+                         "disagree on the blocks or the KV heads")
+    if Hkv <= 0 or Hq % Hkv or Hq // Hkv not in ATTN_GROUPS:
+        raise ValueError(f"{name}: Hq / Hkv = {Hq} / {Hkv} must be one of {ATTN_GROUPS}")
+    if not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError(f"{name} expects contiguous caches")
+    if k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
+        raise ValueError(f"{name}: the caches must be 16-byte aligned")
+    if block_table.shape[0] != S or ctx_lens.shape[0] != S:
+        raise ValueError(f"{name}: block_table {tuple(block_table.shape)} / ctx_lens "
+                         f"{tuple(ctx_lens.shape)} do not match the {S} sequences of {of}")
+    max_blocks = block_table.shape[1]
+    if max_blocks > 1 and block_table.stride(1) != 1:
+        raise ValueError(f"{name} expects contiguous block_table rows")
+    if S > 1 and block_table.stride(0) < max_blocks:
+        raise ValueError(f"{name}: block_table row stride {block_table.stride(0)} must be >= {max_blocks}")
+    if S > 1 and ctx_lens.stride(0) != 1:
+        raise ValueError(f"{name} expects contiguous ctx_lens")
+    if q_start is not None and S > 0 and q_start.stride(0) != 1:
+        raise ValueError(f"{name} expects a contiguous q_start")
+    if S * Hkv >= 2 ** 31 or NB * Hkv >= 2 ** 31 or R >= 2 ** 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 workgroups, cache slabs or rows of q")
+    if out is None:
+        out = torch.empty((R, Hq, D), dtype=torch.bfloat16, device=q.device)
+    if out.dim() != 3 or tuple(out.shape) != (R, Hq, D) or out.dtype != torch.bfloat16:
+        raise ValueError("bad output tensor")
+    slab = Hq * ATTN_HEAD_DIM
+    for nm, t in (("q", q), ("out", out)):
+        if t.stride(2) != 1 or (Hq > 1 and t.stride(1) != ATTN_HEAD_DIM):
+            raise ValueError(f"{name}: {nm} must have contiguous [Hq, {ATTN_HEAD_DIM}] slabs")
+        if R > 1 and (t.stride(0) < slab or t.stride(0) % 8):
+            raise ValueError(f"{name}: {nm} {rows} stride {t.stride(0)} must be >= {slab} "
+                             "and a multiple of 8")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: {nm} must be 16-byte aligned")
+    return (S, Hq, Hkv, NB, max_blocks, out, _row_stride(q, R, slab), _row_stride(out, R, slab),
+            _row_stride(block_table, S, max_blocks))
+
+
+def _named_blocks_bad(block_table: torch.Tensor, ctx_lens: torch.Tensor, NB: int, max_blocks: int):
+    """Two device booleans: a context length outside [0, 32 * max_blocks]; a block id outside [0, NB)
+    among the ceil(ctx / 32) leading entries of a row, the only ones read as block ids."""
+    need = (ctx_lens + (ATTN_BLOCK_TOKENS - 1)) // ATTN_BLOCK_TOKENS
+    named = torch.arange(max_blocks, dtype=torch.int32, device=ctx_lens.device)[None, :] < need[:, None]
+    return (((ctx_lens < 0) | (ctx_lens > ATTN_BLOCK_TOKENS * max_blocks)).any(),
+            (((block_table < 0) | (block_table >= NB)) & named).any())
+
+
 def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
                            ctx_lens: torch.Tensor, out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
                            stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
@@ -307,55 +414,10 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
     [NB, Hkv, 128, 32].  scale defaults to 1 / sqrt(128).  ctx_lens[s] == 0 gives a row of +0.0.
     check=False skips the device-side check of ctx_lens and the block ids (and its sync): for
     callers that guarantee them, and under graph capture."""
-    _check_devices("paged_decode_attention", q, k_cache, v_cache, block_table, ctx_lens, out)
-    if q.dtype != torch.bfloat16 or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16:
-        raise TypeError("paged_decode_attention expects bf16 q, k_cache and v_cache")
-    if block_table.dtype != torch.int32 or ctx_lens.dtype != torch.int32:
-        raise TypeError("paged_decode_attention expects an int32 block_table and ctx_lens")
-    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 or block_table.dim() != 2 or ctx_lens.dim() != 1:
-        raise ValueError("paged_decode_attention expects q [S, Hq, 128], k_cache [NB, Hkv, 32, 128], "
-                         "v_cache [NB, Hkv, 128, 32], block_table [S, max_blocks] and ctx_lens [S]")
-    S, Hq, D = q.shape
-    NB, Hkv, T, Dk = k_cache.shape
-    if D != ATTN_HEAD_DIM or Dk != ATTN_HEAD_DIM or v_cache.shape[2] != ATTN_HEAD_DIM:
-        raise ValueError(f"paged_decode_attention: the head dim must be {ATTN_HEAD_DIM}")
-    if T != ATTN_BLOCK_TOKENS or v_cache.shape[3] != ATTN_BLOCK_TOKENS:
-        raise ValueError(f"paged_decode_attention: the cache block size must be {ATTN_BLOCK_TOKENS} tokens")
-    if tuple(v_cache.shape) != (NB, Hkv, ATTN_HEAD_DIM, ATTN_BLOCK_TOKENS):
-        raise ValueError(f"paged_decode_attention: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} "
-                         "disagree on the blocks or the KV heads")
-    if Hkv <= 0 or Hq % Hkv or Hq // Hkv not in ATTN_GROUPS:
-        raise ValueError(f"paged_decode_attention: Hq / Hkv = {Hq} / {Hkv} must be one of {ATTN_GROUPS}")
-    if not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError("paged_decode_attention expects contiguous caches")
-    if k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
-        raise ValueError("paged_decode_attention: the caches must be 16-byte aligned")
-    if block_table.shape[0] != S or ctx_lens.shape[0] != S:
-        raise ValueError(f"paged_decode_attention: block_table {tuple(block_table.shape)} / ctx_lens "
-                         f"{tuple(ctx_lens.shape)} do not match the {S} sequences of q")
-    max_blocks = block_table.shape[1]
-    if max_blocks > 1 and block_table.stride(1) != 1:
-        raise ValueError("paged_decode_attention expects contiguous block_table rows")
-    if S > 1 and block_table.stride(0) < max_blocks:
-        raise ValueError(f"paged_decode_attention: block_table row stride {block_table.stride(0)} must be >= {max_blocks}")
-    if S > 1 and ctx_lens.stride(0) != 1:
-        raise ValueError("paged_decode_attention expects contiguous ctx_lens")
-    if S * Hkv >= 2 ** 31 or NB * Hkv >= 2 ** 31:
-        raise ValueError("paged_decode_attention: more than 2^31 - 1 workgroups or cache slabs")
-    if out is None:
-        out = torch.empty((S, Hq, D), dtype=torch.bfloat16, device=q.device)
-    if out.dim() != 3 or tuple(out.shape) != (S, Hq, D) or out.dtype != torch.bfloat16:
-        raise ValueError("bad output tensor")
-    slab = Hq * ATTN_HEAD_DIM
-    for name, t in (("q", q), ("out", out)):
-        if t.stride(2) != 1 or (Hq > 1 and t.stride(1) != ATTN_HEAD_DIM):
-            raise ValueError(f"paged_decode_attention: {name} must have contiguous [Hq, {ATTN_HEAD_DIM}] slabs")
-        if S > 1 and (t.stride(0) < slab or t.stride(0) % 8):
-            raise ValueError(f"paged_decode_attention: {name} sequence stride {t.stride(0)} must be >= {slab} "
-                             "and a multiple of 8")
-        if t.data_ptr() % 16:
-            raise ValueError(f"paged_decode_attention: {name} must be 16-byte aligned")
-    ld_q, ld_out, ld_table = _row_stride(q, S, slab), _row_stride(out, S, slab), _row_stride(block_table, S, max_blocks)
+    name = "paged_decode_attention"
+    _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, out)
+    S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table = _paged_attn_operands(
+        name, "sequence", q, k_cache, v_cache, block_table, ctx_lens, out)
     if scale is None:
         scale = ATTN_HEAD_DIM ** -0.5
     if S == 0:
@@ -365,16 +427,70 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
         sp = _stream_ptr(stream, q.device)
         if check:
             with _launch_stream(stream, q.device):
-                need = (ctx_lens + (ATTN_BLOCK_TOKENS - 1)) // ATTN_BLOCK_TOKENS
-                named = torch.arange(max_blocks, dtype=torch.int32, device=q.device)[None, :] < need[:, None]
-                bad = torch.stack([((ctx_lens < 0) | (ctx_lens > ATTN_BLOCK_TOKENS * max_blocks)).any(),
-                                   (((block_table < 0) | (block_table >= NB)) & named).any()]).tolist()    # the one sync
+                bad = torch.stack(_named_blocks_bad(block_table, ctx_lens, NB, max_blocks)).tolist()    # the one sync
             if bad[0]:
-                raise ValueError(f"paged_decode_attention: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
+                raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
             if bad[1]:
-                raise ValueError(f"paged_decode_attention: a block id is outside [0, {NB})")
+                raise ValueError(f"{name}: a block id is outside [0, {NB})")
         h.paged_decode_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
                             ctx_lens.data_ptr(), out.data_ptr(), S, Hq, Hkv, ld_q, ld_out, ld_table, float(scale), sp)
+    return out
+
+
+def paged_prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                            ctx_lens: torch.Tensor, q_start: torch.Tensor, max_q_len: Optional[int] = None,
+                            out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                            stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
+    """Chunked-prefill (append) attention over the paged KV cache of paged_decode_attention.  q and
+    out are [Tq, Hq, 128], packed over the S sequences: the chunk of sequence s is rows q_start[s] ..
+    q_start[s + 1] - 1 (q_start int32 [S + 1], CSR), q_len[s] of them.  ctx_lens[s] counts all tokens
+    of s in the cache, the chunk's own included; query i of the chunk has position
+    p = ctx_lens[s] - q_len[s] + i and
+    out[row, h, :] = bf16(softmax_{t <= p}(scale * q[row, h, :] . K[t, g, :]) . V[t, g, :]), g = h // (Hq // Hkv).
+    q_len[s] == 0 writes nothing; rows outside [q_start[0], q_start[S]) are neither read nor written.
+    max_q_len is an upper bound on every q_len (it sizes the grid); scale defaults to 1 / sqrt(128).
+    check=True verifies ctx_lens, the named block ids, q_start (non-decreasing within [0, Tq]),
+    q_len <= ctx_lens and q_len <= max_q_len on the device first (one sync), and computes max_q_len
+    when it is None.  check=False needs max_q_len and never syncs: for callers that guarantee all of
+    it, and under graph capture."""
+    name = "paged_prefill_attention"
+    _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, q_start, out)
+    S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table = _paged_attn_operands(
+        name, "token", q, k_cache, v_cache, block_table, ctx_lens, out, q_start)
+    Tq = q.shape[0]
+    if max_q_len is None and not check:
+        raise ValueError(f"{name}: check=False needs max_q_len")
+    if max_q_len is not None and not 0 <= max_q_len < 2 ** 31:
+        raise ValueError(f"{name}: max_q_len {max_q_len} is outside [0, 2^31)")
+    if scale is None:
+        scale = ATTN_HEAD_DIM ** -0.5
+    if S == 0 or Tq == 0 or max_q_len == 0:
+        return out
+    h = _native.hip()
+    with torch.cuda.device(q.device):
+        sp = _stream_ptr(stream, q.device)
+        if check:
+            with _launch_stream(stream, q.device):
+                q_len = q_start[1:] - q_start[:-1]
+                bad = torch.stack([b.long() for b in _named_blocks_bad(block_table, ctx_lens, NB, max_blocks)]
+                                  + [((q_len < 0).any() | (q_start[0] < 0) | (q_start[-1] > Tq)).long(),
+                                     (q_len > ctx_lens).any().long(), q_len.max().long()]).tolist()    # the one sync
+            if bad[0]:
+                raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
+            if bad[1]:
+                raise ValueError(f"{name}: a block id is outside [0, {NB})")
+            if bad[2]:
+                raise ValueError(f"{name}: q_start must be non-decreasing within [0, {Tq}]")
+            if bad[3]:
+                raise ValueError(f"{name}: a chunk is longer than its sequence's context (q_len > ctx_lens)")
+            if max_q_len is None:
+                max_q_len = bad[4]
+            elif bad[4] > max_q_len:
+                raise ValueError(f"{name}: a chunk of {bad[4]} tokens is longer than max_q_len = {max_q_len}")
+        if max_q_len:
+            h.paged_prefill_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
+                                 ctx_lens.data_ptr(), q_start.data_ptr(), out.data_ptr(), S, Hq, Hkv, int(max_q_len),
+                                 ld_q, ld_out, ld_table, float(scale), sp)
     return out
 
 

@@ -82,9 +82,10 @@ def _gather_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return out, table, idx, offsets
 
 
-def _attn_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
-    """M sequences of K context tokens, N query heads over o.rows KV heads, in a paged cache of
-    M * K / 32 blocks that a seeded random permutation deals out to the sequences.  The caches
+def _paged_operands(o: Op, q_rows: int, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, q, k_cache, v_cache, table, ctx) of an attention op over M sequences of K context
+    tokens, N query heads over o.rows KV heads and q_rows rows of q, in a paged cache of M * K / 32
+    blocks that a seeded random permutation deals out to the sequences.  q is randn; the caches
     repeat one pattern of values k / 64, |k| <= 127."""
     T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
     if o.K % T:
@@ -92,7 +93,7 @@ def _attn_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     per_seq = o.K // T
     nb = o.M * per_seq
     n = min(nb, ATTN_PATTERN_BLOCKS)
-    q = torch.randn(o.M, o.N, D, generator=g).to(torch.bfloat16).to(device)
+    q = torch.randn(q_rows, o.N, D, generator=g).to(torch.bfloat16).to(device)
 
     def cache(*shape: int) -> torch.Tensor:
         pat = (torch.randint(-127, 128, (n,) + shape, generator=g).float() / 64).to(torch.bfloat16).to(device)
@@ -100,8 +101,22 @@ def _attn_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     kc, vc = cache(o.rows, T, D), cache(o.rows, D, T)
     table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
     ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
-    out = torch.empty(o.M, o.N, D, dtype=torch.bfloat16, device=device)
+    out = torch.empty(q_rows, o.N, D, dtype=torch.bfloat16, device=device)
     return out, q, kc, vc, table, ctx
+
+
+def _attn_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """Decode: one query token per sequence."""
+    return _paged_operands(o, o.M, g, device)
+
+
+def _prefill_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """Prefill: the last o.q of every sequence's K context tokens are its chunk, the chunks packed
+    in sequence order (q_start = arange(M + 1) * q)."""
+    if o.q > o.K:
+        raise ValueError(f"prefill chunk {o.q} is longer than the context {o.K}")
+    q_start = (torch.arange(o.M + 1, dtype=torch.int32) * o.q).to(device)
+    return _paged_operands(o, o.M * o.q, g, device) + (q_start,)
 
 
 def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
@@ -110,7 +125,7 @@ def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
 
 # The launches look their loadgen entry point up when called (tests replace the attributes).  The
 # gather's indices, and the attention's ctx_lens and block ids, are in range by construction: no
-# check, no sync (this runs under graph capture).
+# check, no sync (this runs under graph capture); so are the prefill's q_start and max_q_len.
 def _launch_gemm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     a, bt, bias, c = t
     loadgen.gemm(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
@@ -131,6 +146,11 @@ def _launch_attn(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.paged_decode_attention(q, kc, vc, table, ctx, out=out, stream=st, check=False)
 
 
+def _launch_prefill(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, q, kc, vc, table, ctx, q_start = t
+    loadgen.paged_prefill_attention(q, kc, vc, table, ctx, q_start, max_q_len=o.q, out=out, stream=st, check=False)
+
+
 def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     x, y, z = t
     loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
@@ -139,12 +159,14 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # What the executor knows of an op kind: kind -> (make(o, g, device) -> the operand tuple, drawing
 # from the CPU generator g; launch(o, t, st, budget, blocks), the kind's one loadgen call; the
 # position of the output in the tuple).  Operand layouts: GEMMs (a, bt, bias, c); gather (out,
-# table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); triad (x, y, z), x = y + s z.
+# table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); prefill the same and q_start;
+# triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
     "gather": (_gather_operands, _launch_gather, 0),
     "attn": (_attn_operands, _launch_attn, 0),
+    "prefill": (_prefill_operands, _launch_prefill, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -43,6 +43,15 @@ void paged_decode_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintpt
                        float scale, uintptr_t stream);
 // workgroups of that launch: one per (sequence, KV head)
 int paged_decode_workgroups(int S, int Hkv);
+// Chunked-prefill (append) attention over the same cache -- native/hip/prefill_attn.hip: q / out [Tq, Hq, 128] packed
+// over sequences with token strides ld_q / ld_out, the chunk of sequence s being rows q_start[s] .. q_start[s + 1] - 1
+// (q_start int32 [S + 1]); query i of the chunk has position ctx_lens[s] - q_len[s] + i and attends tokens [0, position].
+// max_q_len bounds every q_len (it sizes the grid); S == 0 or max_q_len == 0 launches nothing
+void paged_prefill_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t block_table, uintptr_t ctx_lens,
+                        uintptr_t q_start, uintptr_t out, int S, int Hq, int Hkv, int max_q_len, int64_t ld_q,
+                        int64_t ld_out, int64_t ld_table, float scale, uintptr_t stream);
+// workgroups of that launch: one per (sequence, KV head, tile of 128 (chunk token, head of the group) columns)
+int paged_prefill_workgroups(int S, int Hq, int Hkv, int max_q_len);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

@@ -41,37 +41,19 @@
 #include <type_traits>
 
 #include "api.h"
-#include "common.h"
+#include "paged_attn.h"
 
 namespace gs {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x8_bits __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kHeadDim = 128;
-constexpr int kBlockTokens = 32;
 constexpr int kWaves = 4;
-constexpr int kMaxGroup = 16;                     // the MFMA's column dimension
 constexpr int kOLd = kHeadDim + 4;                // fp32 row of the LDS image: 528 bytes, 16-byte aligned
-constexpr float kLog2e = 1.44269504088896340736f;
 
 struct Partials {
   float o[kWaves][kMaxGroup][kOLd];
   float m[kWaves][kMaxGroup];
   float l[kWaves][kMaxGroup];
 };
-
-// the 8 K fragments of one (block, KV head) slab: tile t, k-step kk is d = 32 kk + 8 g .. + 7 of
-// the lane's token 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
-__device__ __forceinline__ void load_k(bf16x8 (&kf)[2][4], const __bf16* p) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-      kf[t][kk] = *reinterpret_cast<const bf16x8*>(p + t * 4 * kHeadDim + kk * 32);
-}
 
 __global__ void __launch_bounds__(256, 4) paged_decode_kernel(const __bf16* __restrict__ q,
                                                            const __bf16* __restrict__ k_cache,
@@ -237,8 +219,6 @@ __global__ void __launch_bounds__(256, 4) paged_decode_kernel(const __bf16* __re
   }
 }
 
-bool group_supported(int group) { return group == 1 || group == 2 || group == 4 || group == 8 || group == 16; }
-
 }  // namespace
 
 int paged_decode_workgroups(int S, int Hkv) { return S * Hkv; }
@@ -246,17 +226,9 @@ int paged_decode_workgroups(int S, int Hkv) { return S * Hkv; }
 void paged_decode_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t block_table, uintptr_t ctx_lens,
                        uintptr_t out, int S, int Hq, int Hkv, int64_t ld_q, int64_t ld_out, int64_t ld_table,
                        float scale, uintptr_t stream) {
-  if (S < 0 || Hq <= 0 || Hkv <= 0) throw std::runtime_error("paged_decode: negative or zero sizes");
-  if (Hq % Hkv || !group_supported(Hq / Hkv))
-    throw std::runtime_error("paged_decode: Hq / Hkv must be 1, 2, 4, 8 or 16");
+  check_paged_operands("paged_decode", "sequence", q, k_cache, v_cache, block_table, ctx_lens, out, S, Hq, Hkv, ld_q,
+                       ld_out, ld_table);
   if ((int64_t)S * Hkv >= (int64_t)1 << 31) throw std::runtime_error("paged_decode: more than 2^31 - 1 workgroups");
-  const int64_t slab = (int64_t)Hq * kHeadDim;
-  if (ld_q < slab || ld_out < slab || ld_q % 8 || ld_out % 8)
-    throw std::runtime_error("paged_decode: q / out sequence strides must be >= Hq * 128 and multiples of 8 elements");
-  if (ld_table < 0) throw std::runtime_error("paged_decode: negative block-table stride");
-  if (q % 16 || out % 16 || k_cache % 16 || v_cache % 16)
-    throw std::runtime_error("paged_decode: q / out / k_cache / v_cache must be 16-byte aligned");
-  if (block_table % 4 || ctx_lens % 4) throw std::runtime_error("paged_decode: block_table / ctx_lens must be 4-byte aligned");
   if (S == 0) return;
   hipLaunchKernelGGL(paged_decode_kernel, dim3(paged_decode_workgroups(S, Hkv)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const __bf16*>(q),
