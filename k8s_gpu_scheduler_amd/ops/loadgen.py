@@ -105,13 +105,28 @@ of the conversion and float64 sums):
     normaliser is summed from the fp32 probabilities; the probabilities are rounded to bf16 for
     the P . V MFMA (at most 2^-9 relative each), which accumulates in fp32; the partial results
     of the four waves are merged in fp32, divided by the normaliser (an IEEE division) and rounded
-    to bf16 once.  ctx == 0 gives a row of +0.0;
+    to bf16 once.  ctx == 0 gives a row of +0.0.  A non-finite q, K or V value inside ctx follows the
+    NaN rule for the heads of its (sequence, KV head) and never leaves them: a NaN or +Inf score
+    (Inf - Inf) makes the head's whole row NaN -- the normaliser is NaN, and the division is not
+    guarded against it --, a -Inf score is probability 0, and a non-finite V element poisons only
+    its own d (0 * Inf and 0 * NaN are NaN: no probability-0 token is skipped).  Left unspecified:
+    the row of a head whose -Inf score belongs to the only token inside ctx of the only block its
+    wave takes (the last token of a context of 33, 65 or 97 tokens) -- that wave's running maximum
+    is then -Inf itself;
   * paged_prefill_attention (pinned by tests/test_gpu_prefill_attn_exact.py): the same contract, so
     the decode attention's error derivation carries over -- fp32 q . k on the MFMA, scale on the
     fp32 score, the online softmax in fp32 with exp(x) = 2^(x * log2 e), the normaliser summed from
     the fp32 probabilities, the probabilities rounded to bf16 only as the P . V operand, O in fp32,
     one IEEE division by the normaliser and one bf16 rounding.  A column's running state lives in
-    one wave for the whole walk: there is no merge of partial results.
+    one wave for the whole walk: there is no merge of partial results;
+  * both attentions (pinned by tests/test_gpu_attn_numeric_edges.py on every finite bf16 code as a
+    V element, on rounding ties, exponent carries, subnormal and overflowing sums of two V
+    elements, on NaN / +-Inf planted in q, K and V, and at scale 0, the negated and two other
+    scales): bf16 subnormals pass through the P . V MFMA, the division and the rounding
+    unchanged, 0x7F7F stays finite, an fp32 sum past the range gives +-Inf.  The sign of a zero
+    output is unspecified except for ctx == 0: an accumulator that a rescale by alpha = 0 zeroed
+    keeps the sign of what it held, so V = -0.0 with probability 1, or v + (-v), may give +0.0 or
+    -0.0; a nonzero value that only rounds to zero keeps its own sign.
 """
 from __future__ import annotations
 

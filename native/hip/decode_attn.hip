@@ -213,8 +213,9 @@ __global__ void __launch_bounds__(256, 4) paged_decode_kernel(const __bf16* __re
       }
     }
     bf16x8 r;
+    // lsum == 0 only for ctx == 0 (all four weights 0): +0.0.  A NaN normaliser divides: NaN out
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (__bf16)(lsum > 0.f ? acc[e] / lsum : 0.f);
+    for (int e = 0; e < 8; ++e) r[e] = (__bf16)(lsum == 0.f ? 0.f : acc[e] / lsum);
     *reinterpret_cast<bf16x8*>(out + (size_t)s * ld_out + (size_t)(kvh * group + c) * kHeadDim + d0) = r;
   }
 }
