@@ -28,6 +28,9 @@ A fifth kernel character is "prefill", chunked-prefill attention over the same c
 (ops.loadgen.paged_prefill_attention): many new tokens per sequence attending causally, so every
 cache slab is reused by all of them and the op is MFMA-bound -- but unlike a GEMM's, each of its
 MFMAs sits behind exps, cross-lane maxima and a rescale of the accumulators.
+A sixth is "attn_split", the decode attention of a FEW LONG sequences (LONG_CONTEXT): HBM-bound like
+"attn", but S * Hkv workgroups would leave most CUs idle, so each (sequence, KV head) is split over
+`splits` workgroups whose fp32 partials a second kernel merges -- CU-hungry only when split.
 """
 from __future__ import annotations
 
@@ -37,6 +40,8 @@ from typing import Dict, List, Optional, Tuple
 
 ATTN_HEAD_DIM = 128               # the attention kernels' head dim ...
 ATTN_BLOCK_TOKENS = 32            # ... and KV-cache block size (native/hip/decode_attn.hip, prefill_attn.hip)
+ATTN_MAX_KV_SPLITS = 32           # the split-KV decode attention: most workgroups per (sequence, KV head) ...
+ATTN_PARTIAL_FLOATS = 132         # ... and fp32 per (sequence, head, split) in its workspace: O, m, l, 2 unused
 
 
 @dataclass(frozen=True)
@@ -44,13 +49,15 @@ class Op:
     kind: str              # "gemm" (bf16) | "gemm8" (fp8 e4m3, bf16 out) | "triad" | "gather" (bf16 embedding bag)
     #                        | "attn" (bf16 paged-KV decode attention, head dim 128, blocks of 32 tokens)
     #                        | "prefill" (bf16 paged-KV chunked-prefill attention over the same cache)
-    M: int = 0             # gather: bags; attn, prefill: sequences
-    N: int = 0             # gather: D, the row length; attn, prefill: query heads
-    K: int = 0             # gather: pooling factor (rows per bag); attn, prefill: context tokens per sequence
+    #                        | "attn_split" ("attn" as a split-KV launch pair: `splits` workgroups per (sequence, KV head))
+    M: int = 0             # gather: bags; attn, attn_split, prefill: sequences
+    N: int = 0             # gather: D, the row length; attn, attn_split, prefill: query heads
+    K: int = 0             # gather: pooling factor (rows per bag); attn, attn_split, prefill: context tokens per sequence
     relu: bool = True
     n_floats: int = 0      # triad
-    rows: int = 0          # gather: rows of the table; attn, prefill: KV heads
+    rows: int = 0          # gather: rows of the table; attn, attn_split, prefill: KV heads
     q: int = 0             # prefill: chunk tokens per sequence (the last q of the K context tokens)
+    splits: int = 0        # attn_split: kv_splits, workgroups per (sequence, KV head)
 
     @property
     def is_gemm(self) -> bool:
@@ -65,7 +72,7 @@ class Op:
     def flops(self) -> float:
         if self.kind == "gather":
             return 1.0 * self.M * self.K * self.N                 # one add per gathered element
-        if self.kind == "attn":                                   # q . K^T and P . V, a multiply-add each
+        if self.kind in ("attn", "attn_split"):                   # q . K^T and P . V, a multiply-add each
             return 4.0 * self.M * self.N * self.K * ATTN_HEAD_DIM
         if self.kind == "prefill":                                # the same per (query, token at or below it) pair:
             pairs = self.q * (self.K - self.q) + self.q * (self.q + 1) / 2        # the prefix, then the causal triangle
@@ -80,9 +87,12 @@ class Op:
             return 1.0 * (self.M * self.K + self.N * self.K) + 2.0 * self.M * self.N
         if self.kind == "gather":                                 # rows read, indices, offsets, output
             return 2.0 * self.M * self.K * self.N + 4.0 * self.M * self.K + 4.0 * (self.M + 1) + 2.0 * self.M * self.N
-        if self.kind == "attn":                                   # K and V, q and out, block table, ctx_lens
-            return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.N * ATTN_HEAD_DIM
-                    + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M)
+        if self.kind in ("attn", "attn_split"):                   # K and V, q and out, block table, ctx_lens
+            b = (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.N * ATTN_HEAD_DIM
+                 + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M)
+            if self.kind == "attn_split":                         # the fp32 workspace, written and read once
+                b += 2 * 4.0 * decode_split_workspace_floats(self.M, self.N, self.splits)
+            return b
         if self.kind == "prefill":                                # K and V read once, q and out, table, ctx_lens, q_start
             return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.q * self.N * ATTN_HEAD_DIM
                     + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + 4.0 * (self.M + 1))
@@ -103,6 +113,8 @@ class Op:
             return default_attn_workgroups(self.M, self.rows)
         if self.kind == "prefill":
             return default_prefill_workgroups(self.M, self.N, self.rows, self.q)
+        if self.kind == "attn_split":
+            return default_attn_split_workgroups(self.M, self.rows, self.splits)
         return None
 
 
@@ -207,9 +219,28 @@ STAGED: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "attn_split" kind, which those pinned tables do not list either (they merge into
+# EXTRA with STAGED, when test_op_kinds_cpu.py's tables are next rewritten):
+#   llm_decode_long_8  one Llama-8B-like decoder layer decoding 8 sequences with 32,768 tokens of
+#                      context each -- small-batch, long-context serving.  The 8 new tokens ride in
+#                      the GEMMs' minimum 64-row tile (rows 8 .. 63 are padding): the fused QKV
+#                      projection (64 x 6144 x 4096), split-KV decode attention of 32 query heads
+#                      over 8 KV heads, the output projection (64 x 4096 x 4096).  The paged KV cache
+#                      is exactly 1 GiB (8 x 1,024 blocks x 8 heads x 2 x 8 KiB), as llm_decode_256's,
+#                      and streams from HBM -- but unsplit its grid is 64 workgroups on 256 CUs.
+#                      splits = 4 (256 workgroups, one per CU) is the fastest count of the sweep in
+#                      profiles/r10_decode_split/rates.json for (8 sequences, 32,768 tokens, groups
+#                      of 4): 181 us against 413 us unsplit.  No co-run groups are measured with it yet
+LONG_CONTEXT: Dict[str, Workload] = {
+    "llm_decode_long_8": Workload("llm_decode_long_8", "llm_decode_long", "hip", 8,
+                                  (Op("gemm", 64, 6144, 4096), Op("attn_split", 8, 32, 32768, rows=8, splits=4),
+                                   Op("gemm", 64, 4096, 4096)), 1.25),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra or staged workload by exact name."""
-    for table in (CATALOG, EXTRA, STAGED):
+    """A catalog, extra, staged or long-context workload by exact name."""
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT):
         w = table.get(name)
         if w is not None:
             return w
@@ -219,9 +250,9 @@ def get(name: str) -> Workload:
 def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
-    the catalog, the staged ones after those."""
+    the catalog, the staged ones after those, the long-context ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED):
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -299,6 +330,29 @@ def default_attn_workgroups(S: int, Hkv: int) -> int:
     return S * Hkv
 
 
+def default_attn_split_workgroups(S: int, Hkv: int, kv_splits: int) -> int:
+    """Workgroups of the split-KV decode attention's first launch: one per (sequence, KV head, split)
+    -- a pure-Python copy of paged_decode_split_workgroups (native/hip/decode_attn.hip), pinned
+    against it in tests/test_decode_split_cpu.py.  (The merge launch is ceil(S * Hq / 16).)"""
+    return S * Hkv * kv_splits
+
+
+def decode_split_workspace_floats(S: int, Hq: int, kv_splits: int) -> int:
+    """fp32 elements of the split-KV decode attention's workspace: ATTN_PARTIAL_FLOATS per (sequence,
+    head, split) -- a pure-Python copy of paged_decode_split_workspace_floats, pinned like the above."""
+    return S * Hq * kv_splits * ATTN_PARTIAL_FLOATS
+
+
+def decode_split_range(ctx: int, kv_splits: int, p: int) -> Tuple[int, int]:
+    """The cache blocks [lo, hi) of a sequence of ctx tokens that split p of kv_splits takes -- THE
+    partition rule of the split-KV decode attention (native/hip/decode_attn.hip), part of its
+    contract: with nblk = ceil(ctx / 32) and bps = ceil(nblk / kv_splits), split p takes
+    [p * bps, min(nblk, (p + 1) * bps)) and is empty (lo == hi) where p * bps >= nblk."""
+    nblk = -(-ctx // ATTN_BLOCK_TOKENS)
+    bps = -(-nblk // kv_splits)
+    return min(p * bps, nblk), min((p + 1) * bps, nblk)
+
+
 PREFILL_COLUMNS = 128              # (chunk token, head of the group) columns per workgroup (native/hip/prefill_attn.hip)
 
 
@@ -314,8 +368,8 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
     launches them for `cu_budget` under the default policy (default_gemm_workgroups), gather
-    workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups
-    and default_prefill_workgroups count them, the
+    workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups,
+    default_attn_split_workgroups and default_prefill_workgroups count them, the
     stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""

@@ -7,7 +7,7 @@ e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
 `embedding_bag(table, idx, offsets)` gathers indexed table rows and sums them per bag (random-row
 HBM / cache traffic, no MFMA); `paged_decode_attention(q, k_cache, v_cache, block_table, ctx_lens)`
 is LLM decode attention over a paged KV cache (block-table-indexed HBM traffic, MFMA products, a
-softmax in the loop); `paged_prefill_attention(q, k_cache, v_cache, block_table, ctx_lens, q_start)`
+softmax in the loop; `kv_splits=` spreads a few long sequences over the chip); `paged_prefill_attention(q, k_cache, v_cache, block_table, ctx_lens, q_start)`
 is chunked-prefill (append) attention over the same cache: many new tokens per sequence attending
 causally (MFMA-bound, the softmax inside the matrix loop).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
@@ -113,6 +113,19 @@ of the conversion and float64 sums):
     the row of a head whose -Inf score belongs to the only token inside ctx of the only block its
     wave takes (the last token of a context of 33, 65 or 97 tokens) -- that wave's running maximum
     is then -Inf itself;
+  * paged_decode_attention with kv_splits >= 2 (pinned by tests/test_gpu_decode_split_exact.py): the
+    split rule -- with nblk = ceil(ctx / 32) and bps = ceil(nblk / kv_splits), workgroup p of a
+    (sequence, KV head) takes the blocks [p * bps, min(nblk, (p + 1) * bps)), none where
+    p * bps >= nblk (decode_split_range) -- and the workspace rule -- 132 fp32 per (sequence, head,
+    split): the unnormalised O, the maximum and the normaliser of the split, two unused words;
+    decode_split_workspace_floats(S, Hq, kv_splits) in all, 16-byte aligned, one launch in flight
+    per workspace; every word the merge reads was written by the same launch, so the workspace
+    may hold anything before, NaN included -- are part of the contract.  The numeric contract of
+    the unsplit op carries over with one more fp32 merge level: inside a split everything is as
+    above up to the merge of the four waves, which is left undivided; the splits are merged by the
+    same formula (weight exp(m_p - max m), exactly 0 for an empty split), then the same single
+    IEEE division and the same single bf16 rounding.  ctx == 0 gives a row of +0.0, and the NaN
+    rule is the one above;
   * paged_prefill_attention (pinned by tests/test_gpu_prefill_attn_exact.py): the same contract, so
     the decode attention's error derivation carries over -- fp32 q . k on the MFMA, scale on the
     fp32 score, the online softmax in fp32 with exp(x) = 2^(x * log2 e), the normaliser summed from
@@ -136,6 +149,8 @@ import torch
 
 from .. import _native
 from ..models.workloads import ATTN_BLOCK_TOKENS, ATTN_HEAD_DIM          # the decode-attention kernel's fixed sizes
+from ..models.workloads import (ATTN_MAX_KV_SPLITS, decode_split_range,      # the split-KV decode's rules, pure Python
+                                decode_split_workspace_floats)
 
 BM, BN, BK = 64, 64, 64          # minimum granularity; the tile (128x128 / 64x128 / 64x64) is picked per shape
 
@@ -422,17 +437,41 @@ def _named_blocks_bad(block_table: torch.Tensor, ctx_lens: torch.Tensor, NB: int
 
 def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
                            ctx_lens: torch.Tensor, out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
-                           stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
+                           stream: Optional[torch.cuda.Stream] = None, check: bool = True, kv_splits: int = 1,
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[s, h, :] = bf16(softmax_t(scale * q[s, h, :] . K[t, g, :]) . V[t, g, :]) over the ctx_lens[s]
     tokens of sequence s, g = h // (Hq // Hkv): one new token per sequence against a paged KV cache.
     Token t is slot t % 32 of block block_table[s, t // 32]; k_cache [NB, Hkv, 32, 128], v_cache
     [NB, Hkv, 128, 32].  scale defaults to 1 / sqrt(128).  ctx_lens[s] == 0 gives a row of +0.0.
     check=False skips the device-side check of ctx_lens and the block ids (and its sync): for
-    callers that guarantee them, and under graph capture."""
+    callers that guarantee them, and under graph capture.
+
+    kv_splits == 1 is one workgroup per (sequence, KV head); the workspace is neither needed nor
+    touched.  2 <= kv_splits <= ATTN_MAX_KV_SPLITS is the split-KV launch pair for a few long
+    sequences: kv_splits workgroups per (sequence, KV head), each over the contiguous range of
+    blocks decode_split_range gives it (with nblk = ceil(ctx / 32) and bps = ceil(nblk /
+    kv_splits), split p takes [p * bps, min(nblk, (p + 1) * bps)); empty where p * bps >= nblk),
+    write fp32 partials to `workspace`, and a merge kernel on the same stream combines them.
+    workspace is a contiguous, 16-byte aligned fp32 tensor on the operands' device of at least
+    decode_split_workspace_floats(S, Hq, kv_splits) elements; None allocates one on the launch
+    stream.  One workspace serves ONE launch in flight: two launches on different streams need two,
+    and a caller under graph capture passes its own (it must outlive the graph)."""
     name = "paged_decode_attention"
     _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, out)
     S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table = _paged_attn_operands(
         name, "sequence", q, k_cache, v_cache, block_table, ctx_lens, out)
+    if isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or not 1 <= kv_splits <= ATTN_MAX_KV_SPLITS:
+        raise ValueError(f"{name}: kv_splits = {kv_splits!r} must be an int in [1, {ATTN_MAX_KV_SPLITS}]")
+    if kv_splits > 1 and workspace is not None:
+        need = decode_split_workspace_floats(S, Hq, kv_splits)
+        if workspace.dtype != torch.float32:
+            raise TypeError(f"{name} expects an fp32 workspace")
+        if workspace.device != q.device:
+            raise ValueError(f"{name}: workspace on {workspace.device}, operands on {q.device}")
+        if not workspace.is_contiguous() or workspace.data_ptr() % 16:
+            raise ValueError(f"{name}: workspace must be contiguous and 16-byte aligned")
+        if workspace.numel() < need:
+            raise ValueError(f"{name}: workspace of {workspace.numel()} floats, {kv_splits} splits need {need}")
     if scale is None:
         scale = ATTN_HEAD_DIM ** -0.5
     if S == 0:
@@ -447,8 +486,19 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
                 raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
             if bad[1]:
                 raise ValueError(f"{name}: a block id is outside [0, {NB})")
-        h.paged_decode_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
-                            ctx_lens.data_ptr(), out.data_ptr(), S, Hq, Hkv, ld_q, ld_out, ld_table, float(scale), sp)
+        if kv_splits == 1:
+            h.paged_decode_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
+                                ctx_lens.data_ptr(), out.data_ptr(), S, Hq, Hkv, ld_q, ld_out, ld_table, float(scale),
+                                sp)
+            return out
+        if workspace is None:
+            # from the caching allocator, on the launch stream: its reuse is ordered after the merge
+            with _launch_stream(stream, q.device):
+                workspace = torch.empty(decode_split_workspace_floats(S, Hq, kv_splits), dtype=torch.float32,
+                                        device=q.device)
+        h.paged_decode_split_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
+                                  ctx_lens.data_ptr(), workspace.data_ptr(), out.data_ptr(), S, Hq, Hkv, kv_splits,
+                                  ld_q, ld_out, ld_table, float(scale), sp)
     return out
 
 

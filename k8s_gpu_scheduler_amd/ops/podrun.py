@@ -3,13 +3,15 @@
     python -m k8s_gpu_scheduler_amd.ops.podrun --workload onnx_resnet50_1024 [--iters N]
     python -m k8s_gpu_scheduler_amd.ops.podrun --workload dlrm_2048 --iters 2
     python -m k8s_gpu_scheduler_amd.ops.podrun --workload llm_decode_256 --iters 2
+    python -m k8s_gpu_scheduler_amd.ops.podrun --workload llm_decode_long_8 --iters 2
 
 The device comes from the container env the scheduler wrote (ROCR_VISIBLE_DEVICES /
 HIP_VISIBLE_DEVICES, and HSA_CU_MASK for a Guaranteed share -- the ROCm runtime applies
 them, so the process simply uses device 0); iterations default to the pod's ITERATIONS env.
 The workload is the same kernel mix the bench's executor runs (models.workloads: native
 MFMA GEMMs, HBM stream triads and, for the extra workload dlrm_2048, embedding-bag row gathers
-from a 1 GiB table, for llm_decode_256 decode attention over a 1 GiB paged KV cache), and the GEMM tiles are sized for the pod's CU share
+from a 1 GiB table, for llm_decode_256 decode attention over a 1 GiB paged KV cache, for llm_decode_long_8 its
+split-KV launch pair over 8 sequences of 32,768 tokens), and the GEMM tiles are sized for the pod's CU share
 (`GPU_SCHED_CU` when set).  Prints one JSON line: workload, iterations, wall ms, throughput.
 This is what the e2e tests and the profiling webhook's GPU test launch as a "container".
 """

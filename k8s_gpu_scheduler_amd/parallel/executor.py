@@ -110,6 +110,13 @@ def _attn_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return _paged_operands(o, o.M, g, device)
 
 
+def _attn_split_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """Split-KV decode: the decode operands and the fp32 workspace of the split partials, allocated
+    once per op (one launch of the op is in flight at a time: its stream orders them)."""
+    ws = torch.empty(loadgen.decode_split_workspace_floats(o.M, o.N, o.splits), dtype=torch.float32, device=device)
+    return _paged_operands(o, o.M, g, device) + (ws,)
+
+
 def _prefill_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     """Prefill: the last o.q of every sequence's K context tokens are its chunk, the chunks packed
     in sequence order (q_start = arange(M + 1) * q)."""
@@ -146,6 +153,12 @@ def _launch_attn(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.paged_decode_attention(q, kc, vc, table, ctx, out=out, stream=st, check=False)
 
 
+def _launch_attn_split(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, q, kc, vc, table, ctx, ws = t
+    loadgen.paged_decode_attention(q, kc, vc, table, ctx, out=out, stream=st, check=False, kv_splits=o.splits,
+                                   workspace=ws)
+
+
 def _launch_prefill(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     out, q, kc, vc, table, ctx, q_start = t
     loadgen.paged_prefill_attention(q, kc, vc, table, ctx, q_start, max_q_len=o.q, out=out, stream=st, check=False)
@@ -160,12 +173,13 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # from the CPU generator g; launch(o, t, st, budget, blocks), the kind's one loadgen call; the
 # position of the output in the tuple).  Operand layouts: GEMMs (a, bt, bias, c); gather (out,
 # table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); prefill the same and q_start;
-# triad (x, y, z), x = y + s z.
+# attn_split the same and the workspace; triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
     "gather": (_gather_operands, _launch_gather, 0),
     "attn": (_attn_operands, _launch_attn, 0),
+    "attn_split": (_attn_split_operands, _launch_attn_split, 0),
     "prefill": (_prefill_operands, _launch_prefill, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }

@@ -43,6 +43,18 @@ void paged_decode_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintpt
                        float scale, uintptr_t stream);
 // workgroups of that launch: one per (sequence, KV head)
 int paged_decode_workgroups(int S, int Hkv);
+// The same attention as a split-KV launch pair for a few long sequences (decode_attn.hip tells the partition
+// rule): kv_splits in [2, 32] workgroups per (sequence, KV head) write fp32 partials to `workspace` (16-byte
+// aligned, paged_decode_split_workspace_floats elements, one launch in flight per workspace), a merge kernel
+// on the same stream combines them into out
+void paged_decode_split_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t block_table,
+                             uintptr_t ctx_lens, uintptr_t workspace, uintptr_t out, int S, int Hq, int Hkv,
+                             int kv_splits, int64_t ld_q, int64_t ld_out, int64_t ld_table, float scale,
+                             uintptr_t stream);
+// workgroups of the split kernel: one per (sequence, KV head, split)
+int paged_decode_split_workgroups(int S, int Hkv, int kv_splits);
+// fp32 elements of the workspace: 132 (128 accumulators, maximum, normaliser, 2 unused) per (sequence, head, split)
+size_t paged_decode_split_workspace_floats(int S, int Hq, int kv_splits);
 // Chunked-prefill (append) attention over the same cache -- native/hip/prefill_attn.hip: q / out [Tq, Hq, 128] packed
 // over sequences with token strides ld_q / ld_out, the chunk of sequence s being rows q_start[s] .. q_start[s + 1] - 1
 // (q_start int32 [S + 1]); query i of the chunk has position ctx_lens[s] - q_len[s] + i and attends tokens [0, position].

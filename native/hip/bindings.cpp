@@ -73,6 +73,14 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("ld_q"), py::arg("ld_out"), py::arg("ld_table"), py::arg("scale"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
   m.def("paged_decode_workgroups", &gs::paged_decode_workgroups, py::arg("S"), py::arg("Hkv"));
+  m.def("paged_decode_split_bf16", &gs::paged_decode_split_bf16, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_table"), py::arg("ctx_lens"), py::arg("workspace"), py::arg("out"), py::arg("S"), py::arg("Hq"),
+        py::arg("Hkv"), py::arg("kv_splits"), py::arg("ld_q"), py::arg("ld_out"), py::arg("ld_table"),
+        py::arg("scale"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("paged_decode_split_workgroups", &gs::paged_decode_split_workgroups, py::arg("S"), py::arg("Hkv"),
+        py::arg("kv_splits"));
+  m.def("paged_decode_split_workspace_floats", &gs::paged_decode_split_workspace_floats, py::arg("S"), py::arg("Hq"),
+        py::arg("kv_splits"));
   m.def("paged_prefill_bf16", &gs::paged_prefill_bf16, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_table"), py::arg("ctx_lens"), py::arg("q_start"), py::arg("out"), py::arg("S"), py::arg("Hq"),
         py::arg("Hkv"), py::arg("max_q_len"), py::arg("ld_q"), py::arg("ld_out"), py::arg("ld_table"), py::arg("scale"),
