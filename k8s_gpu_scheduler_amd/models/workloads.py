@@ -31,6 +31,11 @@ MFMAs sits behind exps, cross-lane maxima and a rescale of the accumulators.
 A sixth is "attn_split", the decode attention of a FEW LONG sequences (LONG_CONTEXT): HBM-bound like
 "attn", but S * Hkv workgroups would leave most CUs idle, so each (sequence, KV head) is split over
 `splits` workgroups whose fp32 partials a second kernel merges -- CU-hungry only when split.
+A seventh kernel character is "rope_append" (LLM_LAYER), the rotary embedding of q and K and the append
+of the new K / V to the paged cache (ops.loadgen.rope_append): the one WRITER of that cache -- small,
+latency-dominated and write-scattering (256-byte K rows and, for V, 2-byte-granular columns of the
+transposed [128, 32] slabs, at block-table-named places), no MFMA work, no transcendentals (the caller
+supplies the cos / sin table), and it sits between two GEMM-sized neighbours.
 """
 from __future__ import annotations
 
@@ -50,13 +55,15 @@ class Op:
     #                        | "attn" (bf16 paged-KV decode attention, head dim 128, blocks of 32 tokens)
     #                        | "prefill" (bf16 paged-KV chunked-prefill attention over the same cache)
     #                        | "attn_split" ("attn" as a split-KV launch pair: `splits` workgroups per (sequence, KV head))
-    M: int = 0             # gather: bags; attn, attn_split, prefill: sequences
-    N: int = 0             # gather: D, the row length; attn, attn_split, prefill: query heads
-    K: int = 0             # gather: pooling factor (rows per bag); attn, attn_split, prefill: context tokens per sequence
+    #                        | "rope_append" (bf16 RoPE of q and K and the append of the new K / V to the same cache)
+    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences
+    N: int = 0             # gather: D, the row length; attn, attn_split, prefill, rope_append: query heads
+    K: int = 0             # gather: pooling factor (rows per bag); attn, attn_split, prefill, rope_append: context tokens
+    #                        per sequence (rope_append: the chunk included)
     relu: bool = True
     n_floats: int = 0      # triad
-    rows: int = 0          # gather: rows of the table; attn, attn_split, prefill: KV heads
-    q: int = 0             # prefill: chunk tokens per sequence (the last q of the K context tokens)
+    rows: int = 0          # gather: rows of the table; attn, attn_split, prefill, rope_append: KV heads
+    q: int = 0             # prefill, rope_append: chunk tokens per sequence (the last q of the K context tokens; 1: decode)
     splits: int = 0        # attn_split: kv_splits, workgroups per (sequence, KV head)
 
     @property
@@ -77,6 +84,8 @@ class Op:
         if self.kind == "prefill":                                # the same per (query, token at or below it) pair:
             pairs = self.q * (self.K - self.q) + self.q * (self.q + 1) / 2        # the prefix, then the causal triangle
             return 4.0 * ATTN_HEAD_DIM * self.M * self.N * pairs
+        if self.kind == "rope_append":                            # two multiplies and one add per rotated element of q and K
+            return 3.0 * ATTN_HEAD_DIM * (self.N + self.rows) * self.M * self.q
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -96,6 +105,15 @@ class Op:
         if self.kind == "prefill":                                # K and V read once, q and out, table, ctx_lens, q_start
             return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.q * self.N * ATTN_HEAD_DIM
                     + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + 4.0 * (self.M + 1))
+        if self.kind == "rope_append":
+            tokens = self.M * self.q
+            # table entries (K - q) // 32 .. (K - 1) // 32 of each sequence
+            touched = (self.K - 1) // ATTN_BLOCK_TOKENS - (self.K - self.q) // ATTN_BLOCK_TOKENS + 1 if self.q else 0
+            return (2.0 * tokens * (self.N + 2 * self.rows) * ATTN_HEAD_DIM        # qkv read
+                    + 2.0 * tokens * self.N * ATTN_HEAD_DIM                        # q_out written
+                    + 2.0 * tokens * 2 * self.rows * ATTN_HEAD_DIM                 # K and V written
+                    + 4.0 * ATTN_HEAD_DIM * tokens                                 # one 512-byte cos / sin row per token
+                    + 4.0 * self.M + 4.0 * (self.M + 1) + 4.0 * self.M * touched)  # ctx_lens, q_start, the touched table entries
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -115,6 +133,8 @@ class Op:
             return default_prefill_workgroups(self.M, self.N, self.rows, self.q)
         if self.kind == "attn_split":
             return default_attn_split_workgroups(self.M, self.rows, self.splits)
+        if self.kind == "rope_append":
+            return default_rope_append_workgroups(self.M, self.rows, self.q)
         return None
 
 
@@ -238,9 +258,31 @@ LONG_CONTEXT: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "rope_append" kind, which those pinned tables do not list either: a decoder layer's
+# attention half with the step between the QKV projection and the attention in it -- the fused QKV
+# projection, RoPE of q and K and the append of the new K / V to the paged cache, the attention, the
+# output projection.  Each op keeps its own operands, as everywhere in the executor: the append writes
+# one cache and the attention reads another of the same shape.
+#   llm_layer_decode_256    llm_decode_256 with the append of the 256 new tokens (one per sequence, each
+#                           into slot 31 of its sequence's last block): 2,048 workgroups that each
+#                           rotate five 256-byte rows and scatter 128 2-byte V elements.  Two 1 GiB caches
+#   llm_layer_prefill_2048  llm_prefill_2048 with the append of the two 1,024-token chunks: 528 workgroups,
+#                           512 of them with a whole (block, KV head) slab of K and V to write.  Two 32 MiB
+#                           caches
+# The append is a seventh kernel character; no co-run groups are measured with it yet
+LLM_LAYER: Dict[str, Workload] = {
+    "llm_layer_decode_256": Workload("llm_layer_decode_256", "llm_layer_decode", "hip", 256,
+                                     (Op("gemm", 256, 6144, 4096), Op("rope_append", 256, 32, 1024, rows=8, q=1),
+                                      Op("attn", 256, 32, 1024, rows=8), Op("gemm", 256, 4096, 4096)), 2.25),
+    "llm_layer_prefill_2048": Workload("llm_layer_prefill_2048", "llm_layer_prefill", "hip", 2048,
+                                       (Op("gemm", 2048, 6144, 4096), Op("rope_append", 2, 32, 4096, rows=8, q=1024),
+                                        Op("prefill", 2, 32, 4096, rows=8, q=1024), Op("gemm", 2048, 4096, 4096)), 0.5),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra, staged or long-context workload by exact name."""
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT):
+    """A catalog, extra, staged, long-context or LLM-layer workload by exact name."""
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER):
         w = table.get(name)
         if w is not None:
             return w
@@ -250,9 +292,9 @@ def get(name: str) -> Workload:
 def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
-    the catalog, the staged ones after those, the long-context ones last."""
+    the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT):
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -364,13 +406,23 @@ def default_prefill_workgroups(S: int, Hq: int, Hkv: int, max_q_len: int) -> int
     return S * Hkv * -(-max_q_len * (Hq // Hkv) // PREFILL_COLUMNS)
 
 
+def default_rope_append_workgroups(S: int, Hkv: int, max_q_len: int) -> int:
+    """Workgroups the native RoPE + append launch gets: one per (sequence, KV head, cache block a chunk
+    of max_q_len tokens can touch -- one that starts in slot 31 touches 1 + ceil((max_q_len - 1) / 32)),
+    none where S == 0 or max_q_len == 0 -- a pure-Python copy of rope_append_workgroups
+    (native/hip/rope_append.hip), pinned against it in tests/test_gpu_rope_append_exact.py."""
+    if S == 0 or max_q_len == 0:
+        return 0
+    return S * Hkv * ((max_q_len + 30) // ATTN_BLOCK_TOKENS + 1)
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
     launches them for `cu_budget` under the default policy (default_gemm_workgroups), gather
     workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups,
-    default_attn_split_workgroups and default_prefill_workgroups count them, the
-    stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
+    default_attn_split_workgroups, default_prefill_workgroups and default_rope_append_workgroups count
+    them, the stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
     t = f = 0.0

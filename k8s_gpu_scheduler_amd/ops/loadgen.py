@@ -1,6 +1,6 @@
 """Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
-native/hip/prefill_attn.hip).
+native/hip/prefill_attn.hip, native/hip/rope_append.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
@@ -9,7 +9,9 @@ HBM / cache traffic, no MFMA); `paged_decode_attention(q, k_cache, v_cache, bloc
 is LLM decode attention over a paged KV cache (block-table-indexed HBM traffic, MFMA products, a
 softmax in the loop; `kv_splits=` spreads a few long sequences over the chip); `paged_prefill_attention(q, k_cache, v_cache, block_table, ctx_lens, q_start)`
 is chunked-prefill (append) attention over the same cache: many new tokens per sequence attending
-causally (MFMA-bound, the softmax inside the matrix loop).  Shapes are validated on the host before launch (the kernels
+causally (MFMA-bound, the softmax inside the matrix loop); `rope_append(qkv, cos_sin, k_cache, v_cache,
+block_table, ctx_lens, q_start)` rotates q and K (RoPE) and appends the new K / V to that cache (small,
+latency-dominated, write-scattering).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
@@ -61,7 +63,26 @@ kernels) rely on:
     verifies ctx_lens and the named block ids as above, q_start, q_len <= ctx_lens and
     q_len <= max_q_len on the device first (one sync, which also computes a max_q_len of None);
     check=False needs max_q_len and never syncs.  With every q_len == 1 this is the decode
-    attention.
+    attention;
+  * rope_append (native/hip/rope_append.hip), the writer of that cache: the caches, block_table,
+    ctx_lens, q_start and max_q_len as for the prefill attention, the group rule Hq / Hkv in
+    {1, 2, 4, 8, 16} included; qkv bf16 [Tq, Hq + 2 * Hkv, 128] -- the Hq query heads, then the Hkv K
+    heads, then the Hkv V heads: the output of a fused QKV projection -- with contiguous
+    [Hq + 2 * Hkv, 128] slabs, a token stride >= that slab and a multiple of 8, the first element
+    16-byte aligned; q_out bf16 [Tq, Hq, 128] under the rules of the attentions' out, its storage range
+    disjoint from qkv's (q is not rotated in place); cos_sin fp32 [max_pos, 128], contiguous and
+    16-byte aligned, row p holding 64 cosines and then 64 sines (rope_table computes them in float64
+    on the CPU; the kernel has no transcendentals).  Row q_start[s] + i is token
+    p = ctx_lens[s] - q_len[s] + i of s and goes to slot p % 32 of block block_table[s, p // 32]:
+    rotated K to k_cache[block, g, slot, :], V to v_cache[block, g, :, slot], rotated q to q_out.
+    The kernel trusts all of it: check=True verifies ctx_lens (also against max_pos), q_start,
+    q_len <= ctx_lens, q_len <= max_q_len and, of the block table, the entries the chunks touch --
+    (ctx - q_len) // 32 .. (ctx - 1) // 32 of each sequence with q_len > 0 -- within [0, NB) and
+    pairwise distinct over the launch (two sequences appending into one block is a silent race), on
+    the device first (one sync); check=False needs max_q_len and never syncs.  The grid rule --
+    S * Hkv * ((max_q_len + 30) // 32 + 1) workgroups, workgroup (s, g, j) taking the chunk's tokens in
+    the j-th block the chunk touches, for KV head g -- is part of the contract
+    (models.workloads.default_rope_append_workgroups).
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -77,7 +98,13 @@ they lie above every position, so their scores are replaced by -inf with a selec
 elements by zero.  A non-finite K or V value of a token inside ctx follows the NaN rule below for
 that sequence's queries at or after the token; it leaves the outputs of earlier queries of the same
 sequence unspecified (the token's probability is 0 there, but 0 * NaN in the V fragment the columns
-share cannot be kept out per column); it never reaches another sequence or KV head.
+share cannot be kept out per column); it never reaches another sequence or KV head.  rope_append
+reads the qkv rows [q_start[0], q_start[S]), ctx_lens, q_start, the cos_sin rows of the chunks'
+positions and the touched table entries; it writes the same rows of q_out and, per chunk token and KV
+head, the 128 K elements of the token's slot and its 128 V elements -- every other byte of the caches,
+the earlier slots of the chunk's first block and the slots past ctx of its last included, is
+bit-preserved, and the caches are never read.  q_len == 0 and ctx == 0 write nothing; replaying the
+launch is idempotent.
 
 Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
 of the conversion and float64 sums):
@@ -139,7 +166,15 @@ of the conversion and float64 sums):
     unchanged, 0x7F7F stays finite, an fp32 sum past the range gives +-Inf.  The sign of a zero
     output is unspecified except for ctx == 0: an accumulator that a rescale by alpha = 0 zeroed
     keeps the sign of what it held, so V = -0.0 with probability 1, or v + (-v), may give +0.0 or
-    -0.0; a nonzero value that only rounds to zero keeps its own sign.
+    -0.0; a nonzero value that only rounds to zero keeps its own sign;
+  * rope_append (pinned by tests/test_gpu_rope_append_exact.py): rotate-half pairing (Llama / NeoX) on
+    every q head and every K head -- for i in [0, 64), with x1 = x[i], x2 = x[i + 64],
+    c = cos_sin[p, i] and s = cos_sin[p, 64 + i], all in fp32: y[i] = fma(x1, c, -(x2 * s)) and
+    y[i + 64] = fma(x2, c, x1 * s), the product rounded to fp32, the fma fused, whatever the compiler's
+    contraction setting, then one rounding to bf16 (nearest even, subnormals kept).  A NaN or Inf in
+    x1, x2, c or s reaches both outputs of its pair wherever IEEE says so (0 * NaN and 0 * Inf are NaN:
+    no zero is skipped) and no other element.  V is copied bit for bit, NaN payloads and -0.0
+    included.
 """
 from __future__ import annotations
 
@@ -557,6 +592,135 @@ def paged_prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
                                  ctx_lens.data_ptr(), q_start.data_ptr(), out.data_ptr(), S, Hq, Hkv, int(max_q_len),
                                  ld_q, ld_out, ld_table, float(scale), sp)
     return out
+
+
+ROPE_BASE = 500000.0          # Llama-3's rotary base
+
+
+def rope_table(max_pos: int, base: float = ROPE_BASE) -> torch.Tensor:
+    """The cos_sin operand of rope_append: fp32 [max_pos, 128] on the CPU, row p holding cos(p * f_i) for
+    i in [0, 64) and then sin(p * f_i), f_i = base ** (-i / 64).  The angles and their cosines and sines
+    are computed in float64 and cast once."""
+    if max_pos < 0:
+        raise ValueError(f"rope_table: max_pos {max_pos} is negative")
+    half = ATTN_HEAD_DIM // 2
+    freq = torch.tensor([base ** (-i / half) for i in range(half)], dtype=torch.float64)
+    ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * freq[None, :]
+    return torch.cat([ang.cos(), ang.sin()], dim=1).to(torch.float32)
+
+
+def _storage_range(t: torch.Tensor):
+    """[lo, hi): the bytes between the first and the last element of t, as addresses."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    last = sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                block_table: torch.Tensor, ctx_lens: torch.Tensor, q_start: torch.Tensor,
+                max_q_len: Optional[int] = None, q_out: Optional[torch.Tensor] = None,
+                stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
+    """Rotary position embedding of q and K and the append of the new K / V to the paged KV cache of the
+    attentions.  qkv is [Tq, Hq + 2 * Hkv, 128] -- the Hq query heads, the Hkv K heads, the Hkv V heads,
+    what a fused QKV projection produces --, packed over the S sequences by q_start (int32 [S + 1], CSR)
+    as paged_prefill_attention's q is.  ctx_lens[s] counts the chunk's own tokens: row q_start[s] + i is
+    token p = ctx_lens[s] - q_len[s] + i of s and goes to slot p % 32 of block block_table[s, p // 32].
+    cos_sin is fp32 [max_pos, 128], row p holding 64 cosines and then 64 sines (rope_table).  With
+    x1 = x[i], x2 = x[i + 64], c = cos_sin[p, i] and s = cos_sin[p, 64 + i] for i in [0, 64), in fp32,
+    y[i] = fma(x1, c, -(x2 * s)) and y[i + 64] = fma(x2, c, x1 * s), rounded to bf16 once: the rotated q
+    heads go to q_out [Tq, Hq, 128] (made when None; returned), the rotated K heads to
+    k_cache[block, g, slot, :]; V is copied bit for bit to v_cache[block, g, :, slot].  The caches are
+    never read and nothing else of them is written; q_len[s] == 0 writes nothing; replaying the launch
+    gives the same.  max_q_len is an upper bound on every q_len (it sizes the grid).
+    check=True verifies on the device first (one sync): ctx_lens within [0, 32 * max_blocks] and at most
+    max_pos, q_start non-decreasing within [0, Tq], q_len <= ctx_lens and q_len <= max_q_len (computed
+    when None), the table entries the chunks touch -- (ctx - q_len) // 32 .. (ctx - 1) // 32 of each
+    sequence with q_len > 0 -- within [0, NB) and pairwise distinct over the launch (two sequences
+    appending into one block is a silent race).  check=False needs max_q_len and never syncs: for
+    callers that guarantee all of it, and under graph capture."""
+    name = "rope_append"
+    _check_devices(name, qkv, cos_sin, k_cache, v_cache, block_table, ctx_lens, q_start, q_out)
+    if cos_sin.dtype != torch.float32:
+        raise TypeError(f"{name} expects an fp32 cos_sin")
+    if qkv.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 qkv, k_cache and v_cache")
+    if (qkv.dim() != 3 or cos_sin.dim() != 2 or k_cache.dim() != 4 or v_cache.dim() != 4 or block_table.dim() != 2
+            or ctx_lens.dim() != 1):
+        raise ValueError(f"{name} expects qkv [Tq, Hq + 2 * Hkv, 128], cos_sin [max_pos, 128], k_cache [NB, Hkv, 32, 128], "
+                         "v_cache [NB, Hkv, 128, 32], block_table [S, max_blocks], ctx_lens [S] and q_start [S + 1]")
+    Tq, Ht = qkv.shape[0], qkv.shape[1]
+    Hq = Ht - 2 * k_cache.shape[1]
+    if Hq <= 0:
+        raise ValueError(f"{name}: qkv has {Ht} heads, the caches {k_cache.shape[1]} KV heads: no Hq + 2 * Hkv")
+    slab = Ht * ATTN_HEAD_DIM
+    if qkv.shape[2] != ATTN_HEAD_DIM:
+        raise ValueError(f"{name}: the head dim must be {ATTN_HEAD_DIM}")
+    if qkv.stride(2) != 1 or (Ht > 1 and qkv.stride(1) != ATTN_HEAD_DIM):
+        raise ValueError(f"{name}: qkv must have contiguous [Hq + 2 * Hkv, {ATTN_HEAD_DIM}] slabs")
+    if Tq > 1 and (qkv.stride(0) < slab or qkv.stride(0) % 8):
+        raise ValueError(f"{name}: qkv token stride {qkv.stride(0)} must be >= {slab} and a multiple of 8")
+    ld_qkv = _row_stride(qkv, Tq, slab)
+    # the q heads as a view: the attentions' checks then cover the caches, the table, ctx_lens, q_start, the
+    # head dim, the group, qkv's alignment and q_out
+    S, Hq, Hkv, NB, max_blocks, q_out, _, ld_q_out, ld_table = _paged_attn_operands(
+        name, "token", qkv[:, :Hq], k_cache, v_cache, block_table, ctx_lens, q_out, q_start)
+    if cos_sin.shape[1] != ATTN_HEAD_DIM:
+        raise ValueError(f"{name}: cos_sin must be [max_pos, {ATTN_HEAD_DIM}]: 64 cosines, then 64 sines")
+    if not cos_sin.is_contiguous() or cos_sin.data_ptr() % 16:
+        raise ValueError(f"{name}: cos_sin must be contiguous and 16-byte aligned")
+    max_pos = cos_sin.shape[0]
+    if max_pos >= 2 ** 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 rows of cos_sin")
+    (a0, a1), (b0, b1) = _storage_range(qkv), _storage_range(q_out)
+    if a0 < b1 and b0 < a1:
+        raise ValueError(f"{name}: q_out overlaps qkv (q is not rotated in place: a replayed launch must give the same)")
+    if max_q_len is None and not check:
+        raise ValueError(f"{name}: check=False needs max_q_len")
+    if max_q_len is not None and not 0 <= max_q_len < 2 ** 31:
+        raise ValueError(f"{name}: max_q_len {max_q_len} is outside [0, 2^31)")
+    if S == 0 or Tq == 0 or max_q_len == 0:
+        return q_out
+    h = _native.hip()
+    with torch.cuda.device(qkv.device):
+        sp = _stream_ptr(stream, qkv.device)
+        if check:
+            with _launch_stream(stream, qkv.device):
+                q_len = q_start[1:] - q_start[:-1]
+                first = (ctx_lens - q_len) // ATTN_BLOCK_TOKENS               # floor: negative where q_len > ctx
+                last = (ctx_lens - 1) // ATTN_BLOCK_TOKENS
+                col = torch.arange(max_blocks, dtype=torch.int32, device=qkv.device)[None, :]
+                touched = (col >= first[:, None]) & (col <= last[:, None]) & (q_len > 0)[:, None]
+                # the untouched entries as ids of their own past every block, then equal neighbours after a sort
+                own = NB + torch.arange(S * max_blocks, dtype=torch.int64, device=qkv.device).view(S, max_blocks)
+                ids = torch.where(touched, block_table.long(), own).flatten().sort().values
+                bad = torch.stack([((ctx_lens < 0) | (ctx_lens > ATTN_BLOCK_TOKENS * max_blocks)).any().long(),
+                                   (ctx_lens > max_pos).any().long(),
+                                   ((q_len < 0).any() | (q_start[0] < 0) | (q_start[-1] > Tq)).long(),
+                                   (q_len > ctx_lens).any().long(), q_len.max().long(),
+                                   (((block_table < 0) | (block_table >= NB)) & touched).any().long(),
+                                   (ids[1:] == ids[:-1]).any().long()]).tolist()                # the one sync
+            if bad[0]:
+                raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
+            if bad[1]:
+                raise ValueError(f"{name}: a context length is past the {max_pos} positions of cos_sin")
+            if bad[2]:
+                raise ValueError(f"{name}: q_start must be non-decreasing within [0, {Tq}]")
+            if bad[3]:
+                raise ValueError(f"{name}: a chunk is longer than its sequence's context (q_len > ctx_lens)")
+            if max_q_len is None:
+                max_q_len = bad[4]
+            elif bad[4] > max_q_len:
+                raise ValueError(f"{name}: a chunk of {bad[4]} tokens is longer than max_q_len = {max_q_len}")
+            if bad[5]:
+                raise ValueError(f"{name}: a block id is outside [0, {NB})")
+            if bad[6]:
+                raise ValueError(f"{name}: two chunks append into one cache block")
+        if max_q_len:
+            h.rope_append_bf16(qkv.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                               block_table.data_ptr(), ctx_lens.data_ptr(), q_start.data_ptr(), q_out.data_ptr(), S, Hq,
+                               Hkv, int(max_q_len), int(max_pos), ld_qkv, ld_q_out, ld_table, sp)
+    return q_out
 
 
 def gemm_flops(M: int, N: int, K: int) -> float:

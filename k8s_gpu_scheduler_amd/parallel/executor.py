@@ -126,6 +126,28 @@ def _prefill_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return _paged_operands(o, o.M * o.q, g, device) + (q_start,)
 
 
+def _rope_append_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(q_out, qkv, cos_sin, k_cache, v_cache, table, ctx, q_start): the last o.q of every sequence's K
+    context tokens are its chunk, packed in sequence order; qkv is randn, the caches (M * K / 32 blocks
+    that a seeded random permutation deals out) are what the op writes and start as zeros."""
+    T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
+    if o.K % T:
+        raise ValueError(f"attention context {o.K} is no multiple of {T}")
+    if o.q > o.K:
+        raise ValueError(f"append chunk {o.q} is longer than the context {o.K}")
+    per_seq = o.K // T
+    nb = o.M * per_seq
+    qkv = torch.randn(o.M * o.q, o.N + 2 * o.rows, D, generator=g).to(torch.bfloat16).to(device)
+    cos_sin = loadgen.rope_table(o.K).to(device)
+    kc = torch.zeros(nb, o.rows, T, D, dtype=torch.bfloat16, device=device)
+    vc = torch.zeros(nb, o.rows, D, T, dtype=torch.bfloat16, device=device)
+    table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
+    ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
+    q_start = (torch.arange(o.M + 1, dtype=torch.int32) * o.q).to(device)
+    q_out = torch.empty(o.M * o.q, o.N, D, dtype=torch.bfloat16, device=device)
+    return q_out, qkv, cos_sin, kc, vc, table, ctx, q_start
+
+
 def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return tuple(torch.ones(o.n_floats, dtype=torch.float32, device=device) for _ in range(3))
 
@@ -164,6 +186,11 @@ def _launch_prefill(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.paged_prefill_attention(q, kc, vc, table, ctx, q_start, max_q_len=o.q, out=out, stream=st, check=False)
 
 
+def _launch_rope_append(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    q_out, qkv, cos_sin, kc, vc, table, ctx, q_start = t
+    loadgen.rope_append(qkv, cos_sin, kc, vc, table, ctx, q_start, max_q_len=o.q, q_out=q_out, stream=st, check=False)
+
+
 def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     x, y, z = t
     loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
@@ -173,7 +200,8 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # from the CPU generator g; launch(o, t, st, budget, blocks), the kind's one loadgen call; the
 # position of the output in the tuple).  Operand layouts: GEMMs (a, bt, bias, c); gather (out,
 # table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); prefill the same and q_start;
-# attn_split the same and the workspace; triad (x, y, z), x = y + s z.
+# attn_split the same and the workspace; rope_append (q_out, qkv, cos_sin, k_cache, v_cache, table, ctx,
+# q_start); triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -181,6 +209,7 @@ OP_KINDS = {
     "attn": (_attn_operands, _launch_attn, 0),
     "attn_split": (_attn_split_operands, _launch_attn_split, 0),
     "prefill": (_prefill_operands, _launch_prefill, 0),
+    "rope_append": (_rope_append_operands, _launch_rope_append, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -64,6 +64,17 @@ void paged_prefill_bf16(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintp
                         int64_t ld_out, int64_t ld_table, float scale, uintptr_t stream);
 // workgroups of that launch: one per (sequence, KV head, tile of 128 (chunk token, head of the group) columns)
 int paged_prefill_workgroups(int S, int Hq, int Hkv, int max_q_len);
+// RoPE + append into the same cache -- native/hip/rope_append.hip: qkv [Tq, Hq + 2 Hkv, 128] (q heads, K heads, V heads;
+// token stride ld_qkv), packed over the sequences by q_start like the prefill's q; row q_start[s] + i is token
+// p = ctx_lens[s] - q_len[s] + i of s and goes to slot p % 32 of block block_table[s, p / 32]: q and K rotated
+// (rotate-half pairing, cos_sin fp32 [max_pos, 128]: 64 cosines then 64 sines per position) to q_out [Tq, Hq, 128]
+// (token stride ld_q_out) and k_cache, V copied bit for bit to v_cache.  The caches are never read
+void rope_append_bf16(uintptr_t qkv, uintptr_t cos_sin, uintptr_t k_cache, uintptr_t v_cache, uintptr_t block_table,
+                      uintptr_t ctx_lens, uintptr_t q_start, uintptr_t q_out, int S, int Hq, int Hkv, int max_q_len,
+                      int max_pos, int64_t ld_qkv, int64_t ld_q_out, int64_t ld_table, uintptr_t stream);
+// workgroups of that launch: one per (sequence, KV head, cache block a chunk of max_q_len tokens can touch):
+// S * Hkv * ((max_q_len + 30) / 32 + 1), 0 where S == 0 or max_q_len == 0
+int rope_append_workgroups(int S, int Hkv, int max_q_len);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

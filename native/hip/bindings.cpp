@@ -87,6 +87,11 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
   m.def("paged_prefill_workgroups", &gs::paged_prefill_workgroups, py::arg("S"), py::arg("Hq"), py::arg("Hkv"),
         py::arg("max_q_len"));
+  m.def("rope_append_bf16", &gs::rope_append_bf16, py::arg("qkv"), py::arg("cos_sin"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("block_table"), py::arg("ctx_lens"), py::arg("q_start"), py::arg("q_out"),
+        py::arg("S"), py::arg("Hq"), py::arg("Hkv"), py::arg("max_q_len"), py::arg("max_pos"), py::arg("ld_qkv"),
+        py::arg("ld_q_out"), py::arg("ld_table"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("rope_append_workgroups", &gs::rope_append_workgroups, py::arg("S"), py::arg("Hkv"), py::arg("max_q_len"));
   // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once
   for (int k = 0; k < gs::kNumKnobs; ++k)
     m.def(("set_" + std::string(gs::kKnobs[k].name)).c_str(), [k](int value) { gs::set_knob(gs::Knob(k), value); });
