@@ -190,6 +190,31 @@ def test_pair_reference_is_the_mean_of_the_pair(prefill):
 
 
 # ------------------------------------------------------------------------------------------------
+# the split mode of parts A, B and D
+# ------------------------------------------------------------------------------------------------
+def test_split_counts_cover_empty_splits_and_pairs_within_and_across():
+    assert A.CODE_SPLITS == (2, 4) and A.PAIR_SPLITS == (2, 4) and A.SCALE_SPLITS == (3, 4)
+    assert A.split_sizes(130, 4) == [2, 2, 1, 0] and A.split_sizes(1, 4) == [1, 0, 0, 0] and A.split_sizes(257, 3) == [3, 3, 3]
+    cover = A.split_coverage("codes", 4)
+    assert {1} <= set(cover["empty"]) and cover["splits with a target"] == [0, 1, 2, 3]
+    assert A.split_coverage("codes", 2)["splits with a target"] == [0, 1]
+    for k in A.PAIR_SPLITS:
+        cover = A.split_coverage("pairs", k)
+        assert cover["within"] >= 2 and cover["across"] >= 2 and cover["within"] + cover["across"] == 8
+
+
+def test_split_counts_of_the_scale_cases_are_uneven_at_three():
+    for part in ("scale 0", "negated", "random"):
+        assert A.split_coverage(part, 3)["uneven"] >= 1
+        A.split_coverage(part, 4)
+    assert A.split_sizes(256, 3) == [3, 3, 2] and A.split_sizes(129, 3) == [2, 2, 1]
+    for ops in (A.zero_scale_ops(False), A.negated_scale_ops()):
+        assert A.order_free_sums(ops)
+    assert not A.order_free_sums(A.softmax_case(False))
+    assert A.lonely_target(A.negated_scale_ops())
+
+
+# ------------------------------------------------------------------------------------------------
 # C. planted values
 # ------------------------------------------------------------------------------------------------
 CASES = [pytest.param(m, n, id=("prefill-" if m else "decode-") + n) for m in (False, True) for n in A.PLANTS[m]]

@@ -40,6 +40,15 @@ pattern.  NaNs are compared by class, everything else bitwise.
      share the rest), and the random regime of the exact modules at 2^-4 and 2^-3 against the
      float64 softmax at that scale.
 
+Parts A, B and D also run through the split-KV launch pair (decode with kv_splits >= 2: a second place
+where partials are weighed, summed, divided and rounded, behind a global-memory workspace): A at 2 and 4
+splits (at 4 the one-block contexts have empty splits), B at 2 and 4 on the same layout, which by the
+partition rule (SPL.split_of) holds pairs whose two tokens lie in different splits and pairs that share
+one -- the expectation stays the one fp32 sum, one division, one rounding --, D at 3 splits (uneven: bps
+does not divide nblk) and 4.  What the split counts cover is asserted by `split_coverage` on the operands
+alone.  The workspace is the split module's guarded window, NaN-filled before every launch: a word the
+merge reads without this launch having written it poisons the output.
+
 Every launch runs guarded as in the two exact modules: q a window of a NaN-filled allocation (with
 NaN rows before and after the chunks for prefill), out a window of a SENT16-filled allocation
 compared bitwise, NaN in the blocks no table entry names and in the slots past ctx, SENT32 around
@@ -55,8 +64,9 @@ import pytest
 import torch
 
 import test_gpu_decode_attn_exact as ATT
+import test_gpu_decode_split_exact as SPL
 import test_gpu_prefill_attn_exact as PRE
-from test_gpu_kernels_exact import NAN, SENT16, guarded_input, guarded_output, guards_intact
+from test_gpu_kernels_exact import NAN, SENT16, SENT32, guarded_input, guarded_output, guarded_vector, guards_intact
 from test_gpu_numeric_edges import bf16_bits_rne, bf16_to_bits, bits_to_f32, edges_match, f32_is_nan, f32_to_bits
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +81,12 @@ MEASURED = """
   The seven decode q and K cases of part C are the ones that see a merge which guards its division with
   `lsum > 0`: it writes +0.0 in exactly their dependants ("[4, 5, 0] got=0x0000 exp=NaN").
   The module: 45 tests in 5 s.
+  Split mode (16 tests in 0.9 s; the module is now 61 tests in 3 s): every finite code came out unchanged at 2 and
+  4 splits and every group size, every zero as +0.0; pairs: 4 within one split and 4 across two at 2 splits, 2 and 6
+  at 4, each of the 1404 exactly-zero sums +0.0; random regime at 3 and 4 splits 0.00112 (scale 2^-4) and 0.00216
+  (2^-3), the unsplit launch's figures.  A merge that weighs every non-empty split by 1 fails A, B, the negated
+  scale ("[4, 1, 0] got=0xbe59 exp=0xbe20": ctx 33, the head whose target is alone in split 1) and the random
+  regime (0.123 and 0.359), not scale 0; a split launch that ignores `scale` fails all of part D.
 """
 
 D, T, SCALE, C0, R0 = ATT.D, ATT.T, ATT.SCALE, ATT.C0, PRE.R0
@@ -522,6 +538,63 @@ def max_abs_score(ops, scale):
 
 
 # ------------------------------------------------------------------------------------------------
+# the split mode of parts A, B and D: what a split count covers, by the split module's partition rule
+# ------------------------------------------------------------------------------------------------
+CODE_SPLITS = (2, 4)
+PAIR_SPLITS = (2, 4)
+SCALE_SPLITS = (3, 4)               # 3 is uneven on every part D case; 4 the power of two
+
+
+def split_sizes(ctx, kv_splits):
+    """Blocks per split, by the partition rule."""
+    return [hi - lo for lo, hi in (SPL.split_range(ctx, kv_splits, p) for p in range(kv_splits))]
+
+
+def split_coverage(part, kv_splits):
+    """Asserts on the operands alone what a split count covers for a part, and returns the figures."""
+    if part == "codes":
+        ctxs, _, targets, _, _, _ = code_layout()
+        empty = {c for c in set(ctxs) if 0 in split_sizes(c, kv_splits)}
+        used = {SPL.split_of(t, c, kv_splits) for c, ts in zip(ctxs, targets) for t in ts}
+        assert len(used) >= 2 and 0 in used                                 # targets in the first and in later splits
+        if kv_splits == 4:
+            one_block = {c for c in set(ctxs) if c <= T}
+            assert one_block and one_block <= empty                         # the one-block contexts have empty splits
+            assert any(split_sizes(c, 4).count(0) == 0 for c in set(ctxs))  # ... beside sequences that fill all four
+        return {"empty": sorted(empty), "splits with a target": sorted(used)}
+    if part == "pairs":
+        targets, _, _ = pair_layout()
+        shared = [SPL.split_of(t, ctx, kv_splits) == SPL.split_of(u, ctx, kv_splits)
+                  for ctx, tg in zip(PAIR_CTXS, targets) for t, u in tg]
+        assert any(shared) and not all(shared)                              # pairs within one split, pairs across two
+        # ... and of each kind one whose d run holds the two overflow entries: Inf from a walk and from the merge
+        over = [bool((pair_entry(s, kv) >= len(pair_table()) - 2).any()) for s in range(len(PAIR_CTXS)) for kv in range(PAIR_HKV)]
+        assert {sh for sh, o in zip(shared, over) if o} == {True, False}
+        return {"within": sum(shared), "across": len(shared) - sum(shared)}
+    ctxs = {"scale 0": ATT.CTX_UNIFORM, "negated": NEG_CTXS, "random": ATT.CTX_B}[part]
+    sizes = [[n for n in split_sizes(c, kv_splits) if n] for c in ctxs if c]
+    uneven = [sz for sz in sizes if len(set(sz)) > 1]
+    if kv_splits == 3:
+        assert uneven                                                       # bps does not divide nblk
+    assert any(len(sz) >= 3 for sz in sizes) and any(len(sz) < kv_splits for sz in sizes)         # and empty splits
+    return {"uneven": len(uneven), "sequences": len(sizes)}
+
+
+def lonely_target(ops):
+    """The negated-scale case holds a split whose only token is some head's target: ctx 33 has token 32
+    alone in block 1, which is split 1 at every split count, and it has probability 0 for a head."""
+    s = ops.ctxs.index(T + 1)
+    p = probabilities(ops, s, 0, -SCALE)[0]                                 # [group, 33]
+    return all(split_sizes(T + 1, k)[:2] == [1, 1] for k in SCALE_SPLITS) and bool((p[:, T] == 0).any())
+
+
+def order_free_sums(ops):
+    """The V of the scale-0 and negated-scale cases are integers in [-4, 4] over at most 257 tokens: every
+    partial sum, in any order and over any split, is an integer below 2^24 -- exact in fp32."""
+    return all(torch.equal(v, v.round()) and float(v.abs().max()) <= 4 for v in ops.vs if v.numel()) and 4 * max(ops.ctxs) < 1 << 24
+
+
+# ------------------------------------------------------------------------------------------------
 # GPU plumbing
 # ------------------------------------------------------------------------------------------------
 class Launch:
@@ -556,12 +629,25 @@ class Launch:
         assert self.q.data_ptr() % 16 == 0 and self.out.data_ptr() % 16 == 0 and self.q.stride(0) == W + C0
         return self
 
-    def run(self, what, scale=None):
+    def run(self, what, scale=None, kv_splits=1):
+        """kv_splits >= 2 (decode only) is the split-KV launch pair with the caller's workspace: the split
+        module's guarded window of exactly the floats the launch needs, all NaN before the launch."""
         from k8s_gpu_scheduler_amd.ops import loadgen
         self.raw.fill_(SENT16)
         if self.ops.decode:
-            loadgen.paged_decode_attention(self.q, self.kc, self.vc, self.table, self.ctx, out=self.out, scale=scale)
+            kw = {}
+            if kv_splits > 1:
+                n = loadgen.decode_split_workspace_floats(self.ops.R, self.ops.Hq, kv_splits)
+                ws_raw, ws = guarded_vector(n, SPL.WS_BEFORE, SPL.WS_AFTER, "cuda")
+                assert ws.data_ptr() % 16 == 0 and ws.numel() == n
+                ws.fill_(NAN)
+                kw = dict(kv_splits=kv_splits, workspace=ws)
+            loadgen.paged_decode_attention(self.q, self.kc, self.vc, self.table, self.ctx, out=self.out, scale=scale, **kw)
+            if kv_splits > 1:
+                torch.cuda.synchronize()
+                assert guards_intact(ws_raw, slice(SPL.WS_BEFORE, SPL.WS_BEFORE + n), SENT32), ("write outside the workspace", what)
         else:
+            assert kv_splits == 1
             loadgen.paged_prefill_attention(self.q, self.kc, self.vc, self.table, self.ctx, self.q_start, out=self.out,
                                             scale=scale)
         torch.cuda.synchronize()
@@ -594,9 +680,40 @@ def test_every_finite_code_passes_through(group, prefill):
     assert_cells(got, codes, nan, ("codes", group, prefill), either_zero=either)
 
 
+@pytest.mark.parametrize("kv_splits", CODE_SPLITS)
+@pytest.mark.parametrize("group", CODE_GROUPS)
+def test_every_finite_code_passes_through_the_split_launch(group, kv_splits):
+    """The target's split has m = 362 and l = 1; every other non-empty split has m = 0 and merge weight
+    exp2(-362 log2 e) = 0, an empty one m = -inf and weight 0: the merged row is the code."""
+    split_coverage("codes", kv_splits)
+    ops = code_ops(group, False)
+    codes = code_expected(ops)
+    either = (codes & 0x7FFF) == 0
+    exp, nan = expected_bits(reference(ops))
+    assert not cell_mismatches(exp, codes, nan, either).any() and not nan.any()
+    got = launch(ops).run(("codes", group, "split", kv_splits), kv_splits=kv_splits)
+    assert_cells(got, codes, nan, ("codes", group, "split", kv_splits), either_zero=either)
+
+
 # ------------------------------------------------------------------------------------------------
 # B. pairs
 # ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kv_splits", PAIR_SPLITS)
+def test_pairs_sum_divide_and_round_through_the_split_launch(kv_splits):
+    """A pair across two splits: each partial is the token's V with m = 362 and l = 1, the merge weighs both
+    by exactly 1 and adds them in fp32; a pair within one split is added by that split's walk.  Either way
+    one fp32 sum, one division by 2, one rounding -- and Inf for the two overflow pairs."""
+    cover = split_coverage("pairs", kv_splits)
+    ops = pair_ops(False)
+    ref = reference(ops, fp32=True)
+    exp, nan = expected_bits(ref)
+    assert not nan.any() and bool((exp == 0x7F80).any()) and bool((exp == 0xFF80).any())
+    got = launch(ops).run(("pairs", "split", kv_splits), kv_splits=kv_splits)
+    print(f"pairs, {kv_splits} splits: {cover['within']} pairs within one split, {cover['across']} across two; "
+          f"{int((got >> 15)[ref == 0].sum())} of {int((ref == 0).sum())} exactly-zero cells came out as -0.0")
+    assert_cells(got, exp, nan, ("pairs", "split", kv_splits), either_zero=ref == 0)
+
+
 @MODES
 def test_pairs_sum_divide_and_round(prefill):
     ops = pair_ops(prefill)
@@ -673,3 +790,47 @@ def test_random_regime_at_other_scales(scale, prefill):
     print(f"{'prefill' if prefill else 'decode'} attention, random regime at scale {scale}: max|out - ref| = {err:.5f} "
           f"(bound {ATT.RANDOM_BOUND * vmax:.5f}, max|V| = {vmax:.4f}, max|score| = {worst:.2f})")
     assert err <= ATT.RANDOM_BOUND * vmax, (scale, prefill, err)
+
+
+@pytest.mark.parametrize("kv_splits", SCALE_SPLITS)
+def test_scale_zero_is_the_uniform_mean_through_the_split_launch(kv_splits):
+    """Every split has m = 0 and merge weight 1; its normaliser is its token count."""
+    split_coverage("scale 0", kv_splits)
+    ops = zero_scale_ops(False)
+    assert order_free_sums(ops)
+    exp, nan = zero_scale_expected(ops)
+    got = launch(ops).run(("scale 0", "split", kv_splits), scale=0.0, kv_splits=kv_splits)
+    assert_cells(got, exp, nan, ("scale 0", "split", kv_splits))
+
+
+@pytest.mark.parametrize("kv_splits", SCALE_SPLITS)
+def test_negated_scale_gives_the_target_probability_zero_through_the_split_launch(kv_splits):
+    """A split that holds a target has m = 0 from its other tokens -- or, where the target is its only
+    token (ctx 33: token 32 alone in block 1), m = -362 and l = 1, which the merge must weigh by
+    exp2(-362 log2 e) = 0 beside the other splits' m = 0."""
+    split_coverage("negated", kv_splits)
+    ops = negated_scale_ops()
+    assert order_free_sums(ops)
+    assert lonely_target(ops)
+    ref = reference(ops, scale=-SCALE)
+    assert bool(exact_in_fp32(ref).all())
+    exp, nan = expected_bits(ref)
+    got = launch(ops).run(("scale -1/sqrt(128)", "split", kv_splits), scale=-SCALE, kv_splits=kv_splits)
+    assert_cells(got, exp, nan, ("scale -1/sqrt(128)", "split", kv_splits))
+
+
+@pytest.mark.parametrize("kv_splits", SCALE_SPLITS)
+@pytest.mark.parametrize("scale", RANDOM_SCALES, ids=["2^-4", "2^-3"])
+def test_random_regime_at_other_scales_through_the_split_launch(scale, kv_splits):
+    split_coverage("random", kv_splits)
+    ops = softmax_case(False)
+    worst = max_abs_score(ops, scale)
+    assert worst <= SCORE_CAP, worst
+    ln = launch(ops)
+    ref = ATT.reference(ln.q_cpu, ln.kc_cpu, ln.vc_cpu, ln.table_cpu, ln.ctx_cpu, scale=scale)
+    got = bits_to_f32(ln.run(("random", scale, "split", kv_splits), scale=scale, kv_splits=kv_splits) << 16).double()
+    vmax = max(float(v.abs().max()) for v in ops.vs if v.numel())
+    err = (got - ref).abs().max().item()
+    print(f"split decode attention ({kv_splits} splits), random regime at scale {scale}: max|out - ref| = {err:.5f} "
+          f"(bound {ATT.RANDOM_BOUND * vmax:.5f}, max|V| = {vmax:.4f}, max|score| = {worst:.2f})")
+    assert err <= ATT.RANDOM_BOUND * vmax, (scale, kv_splits, err)
