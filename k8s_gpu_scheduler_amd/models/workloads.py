@@ -36,6 +36,12 @@ of the new K / V to the paged cache (ops.loadgen.rope_append): the one WRITER of
 latency-dominated and write-scattering (256-byte K rows and, for V, 2-byte-granular columns of the
 transposed [128, 32] slabs, at block-table-named places), no MFMA work, no transcendentals (the caller
 supplies the cos / sin table), and it sits between two GEMM-sized neighbours.
+An eighth is "add_rmsnorm" (LLM_BLOCK), the residual add + RMSNorm in front of a decoder block's projections
+(ops.loadgen.add_rmsnorm): a row reduction followed by a second pass over the same row, kept in registers --
+two bf16 streams in, two out, a cross-lane and cross-wave sum per row, no MFMA work.
+A ninth is "swiglu" (LLM_BLOCK), silu(gate) * up between the fused gate / up projection and the down projection
+(ops.loadgen.swiglu): an element-wise stream like the triad, but bf16, pairing column j with column F + j of the
+same row, and with a transcendental and an IEEE division -- about 20 VALU operations -- per 6 bytes.
 """
 from __future__ import annotations
 
@@ -56,8 +62,11 @@ class Op:
     #                        | "prefill" (bf16 paged-KV chunked-prefill attention over the same cache)
     #                        | "attn_split" ("attn" as a split-KV launch pair: `splits` workgroups per (sequence, KV head))
     #                        | "rope_append" (bf16 RoPE of q and K and the append of the new K / V to the same cache)
-    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences
-    N: int = 0             # gather: D, the row length; attn, attn_split, prefill, rope_append: query heads
+    #                        | "add_rmsnorm" (bf16 residual add + RMSNorm of M rows of N elements, always with a residual)
+    #                        | "swiglu" (bf16 silu(gate) * up: M rows of 2 N in, M rows of N out)
+    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu: rows
+    N: int = 0             # gather: D, the row length; attn, attn_split, prefill, rope_append: query heads;
+    #                        add_rmsnorm: D, the row length; swiglu: F, the output row length
     K: int = 0             # gather: pooling factor (rows per bag); attn, attn_split, prefill, rope_append: context tokens
     #                        per sequence (rope_append: the chunk included)
     relu: bool = True
@@ -86,6 +95,10 @@ class Op:
             return 4.0 * ATTN_HEAD_DIM * self.M * self.N * pairs
         if self.kind == "rope_append":                            # two multiplies and one add per rotated element of q and K
             return 3.0 * ATTN_HEAD_DIM * (self.N + self.rows) * self.M * self.q
+        if self.kind == "add_rmsnorm":                            # the add, the square and its sum, the two multiplies
+            return 5.0 * self.M * self.N
+        if self.kind == "swiglu":                                 # two multiplies, the exp as one, an add, a division, a multiply
+            return 6.0 * self.M * self.N
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -114,6 +127,10 @@ class Op:
                     + 2.0 * tokens * 2 * self.rows * ATTN_HEAD_DIM                 # K and V written
                     + 4.0 * ATTN_HEAD_DIM * tokens                                 # one 512-byte cos / sin row per token
                     + 4.0 * self.M + 4.0 * (self.M + 1) + 4.0 * self.M * touched)  # ctx_lens, q_start, the touched table entries
+        if self.kind == "add_rmsnorm":                            # x and residual read, residual_out and y written, the weight
+            return 8.0 * self.M * self.N + 2.0 * self.N
+        if self.kind == "swiglu":                                 # gate and up read, out written
+            return 6.0 * self.M * self.N
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -135,6 +152,10 @@ class Op:
             return default_attn_split_workgroups(self.M, self.rows, self.splits)
         if self.kind == "rope_append":
             return default_rope_append_workgroups(self.M, self.rows, self.q)
+        if self.kind == "add_rmsnorm":
+            return default_add_rmsnorm_workgroups(self.M)
+        if self.kind == "swiglu":
+            return default_swiglu_workgroups(self.M, self.N)
         return None
 
 
@@ -280,9 +301,42 @@ LLM_LAYER: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "add_rmsnorm" and "swiglu" kinds, which those pinned tables do not list either: a WHOLE
+# Llama-8B-like decoder block (hidden 4096, 32 query heads over 8 KV heads, MLP width 14336) -- residual add +
+# RMSNorm, the fused QKV projection, RoPE + append, the attention, the output projection, residual add + RMSNorm,
+# the fused gate / up projection (N = 2 x 14336), SwiGLU, the down projection.  The MLP is the block's dominant
+# GEMM work.  No GEMM has a ReLU, as in the model.  Each op keeps its own operands, as everywhere in the executor.
+#   llm_block_decode_256    llm_layer_decode_256 with both norms and the MLP: the norms are 256 workgroups
+#                           of one 8 KiB row each, the SwiGLU 448 workgroups over 256 x 14336 outputs -- all
+#                           three latency-dominated beside GEMMs that stream 48 to 224 MiB of weights.  Two
+#                           1 GiB caches and 0.5 GiB of weights and activations
+#   llm_block_prefill_2048  llm_layer_prefill_2048 with both norms and the MLP: 2,048 rows, the SwiGLU 3,584
+#                           workgroups reading 112 MiB and writing 56 MiB
+# The norm and the activation are the eighth and ninth kernel characters; no co-run groups are measured with
+# them yet
+_BLOCK_D, _BLOCK_F = 4096, 14336
+
+
+def _llm_block(rows: int, append: Op, attention: Op) -> Tuple[Op, ...]:
+    return (Op("add_rmsnorm", rows, _BLOCK_D), Op("gemm", rows, 6144, _BLOCK_D, relu=False), append, attention,
+            Op("gemm", rows, _BLOCK_D, 4096, relu=False), Op("add_rmsnorm", rows, _BLOCK_D),
+            Op("gemm", rows, 2 * _BLOCK_F, _BLOCK_D, relu=False), Op("swiglu", rows, _BLOCK_F),
+            Op("gemm", rows, _BLOCK_D, _BLOCK_F, relu=False))
+
+
+LLM_BLOCK: Dict[str, Workload] = {
+    "llm_block_decode_256": Workload("llm_block_decode_256", "llm_block_decode", "hip", 256,
+                                     _llm_block(256, Op("rope_append", 256, 32, 1024, rows=8, q=1),
+                                                Op("attn", 256, 32, 1024, rows=8)), 2.5),
+    "llm_block_prefill_2048": Workload("llm_block_prefill_2048", "llm_block_prefill", "hip", 2048,
+                                       _llm_block(2048, Op("rope_append", 2, 32, 4096, rows=8, q=1024),
+                                                  Op("prefill", 2, 32, 4096, rows=8, q=1024)), 1.25),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra, staged, long-context or LLM-layer workload by exact name."""
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER):
+    """A catalog, extra, staged, long-context, LLM-layer or LLM-block workload by exact name."""
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK):
         w = table.get(name)
         if w is not None:
             return w
@@ -292,9 +346,10 @@ def get(name: str) -> Workload:
 def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
-    the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones last."""
+    the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones, the LLM-block
+    ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER):
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -416,13 +471,30 @@ def default_rope_append_workgroups(S: int, Hkv: int, max_q_len: int) -> int:
     return S * Hkv * ((max_q_len + 30) // ATTN_BLOCK_TOKENS + 1)
 
 
+def default_add_rmsnorm_workgroups(T: int) -> int:
+    """Workgroups the native add + RMSNorm launch gets: one per row -- a pure-Python copy of
+    add_rmsnorm_workgroups (native/hip/rmsnorm.hip), pinned against it in tests/test_norm_act_cpu.py."""
+    return T
+
+
+SWIGLU_CHUNKS_PER_WORKGROUP = 1024     # 16-byte output chunks per workgroup: 256 threads x 4 (native/hip/swiglu.hip)
+
+
+def default_swiglu_workgroups(T: int, F: int) -> int:
+    """Workgroups the native SwiGLU launch gets: the work is flattened over (row, 16-byte chunk of 8
+    outputs) and a workgroup takes 1,024 consecutive chunks, so ceil(T * F / 8192) -- a pure-Python copy of
+    swiglu_workgroups (native/hip/swiglu.hip), pinned against it in tests/test_norm_act_cpu.py."""
+    return -(-(T * (F // 8)) // SWIGLU_CHUNKS_PER_WORKGROUP)
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
     launches them for `cu_budget` under the default policy (default_gemm_workgroups), gather
     workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups,
     default_attn_split_workgroups, default_prefill_workgroups and default_rope_append_workgroups count
-    them, the stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
+    them, the norm's one workgroup per row (default_add_rmsnorm_workgroups) and the SwiGLU's one per 8,192
+    outputs (default_swiglu_workgroups), the stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
     t = f = 0.0

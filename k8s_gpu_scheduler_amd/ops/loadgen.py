@@ -1,6 +1,6 @@
 """Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
-native/hip/prefill_attn.hip, native/hip/rope_append.hip).
+native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
@@ -11,7 +11,10 @@ softmax in the loop; `kv_splits=` spreads a few long sequences over the chip); `
 is chunked-prefill (append) attention over the same cache: many new tokens per sequence attending
 causally (MFMA-bound, the softmax inside the matrix loop); `rope_append(qkv, cos_sin, k_cache, v_cache,
 block_table, ctx_lens, q_start)` rotates q and K (RoPE) and appends the new K / V to that cache (small,
-latency-dominated, write-scattering).  Shapes are validated on the host before launch (the kernels
+latency-dominated, write-scattering); `add_rmsnorm(x, weight, residual)` is the residual add + RMSNorm in
+front of a decoder block's projections (a row reduction and a second pass over the same row, two bf16
+streams in and two out) and `swiglu(gate_up)` the activation between its fused gate / up and down
+projections (an element-wise bf16 stream with an exponential and an IEEE division per element).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
@@ -82,7 +85,22 @@ kernels) rely on:
     the device first (one sync); check=False needs max_q_len and never syncs.  The grid rule --
     S * Hkv * ((max_q_len + 30) // 32 + 1) workgroups, workgroup (s, g, j) taking the chunk's tokens in
     the j-th block the chunk touches, for KV head g -- is part of the contract
-    (models.workloads.default_rope_append_workgroups).
+    (models.workloads.default_rope_append_workgroups);
+  * add_rmsnorm (native/hip/rmsnorm.hip): x, residual, residual_out and out bf16 [T, D], each 2-D with
+    contiguous rows, a row stride >= D and a multiple of 8, the first element 16-byte aligned (every
+    16-byte chunk of a row then is); D a multiple of 8 in [8, 8192] (a thread keeps at most four chunks
+    of its row in registers), T < 2^31; weight bf16 [D], contiguous and 16-byte aligned; eps finite and
+    >= 0, rounded to fp32 once on the host.  residual_out needs a residual.  residual_out may be exactly
+    residual (same data_ptr, shape and strides: the in-place update of the residual stream; a replayed
+    graph is then not idempotent -- every replay adds x again); any other overlap of the storage ranges
+    of out with x, weight, residual or residual_out, or of residual_out with x, weight or residual,
+    raises.  One workgroup per row (models.workloads.default_add_rmsnorm_workgroups);
+  * swiglu (native/hip/swiglu.hip): gate_up bf16 [T, 2F] -- gate columns [0, F), up columns [F, 2F): the
+    output of a fused gate / up projection -- and out bf16 [T, F] under the same row rules; F a positive
+    multiple of 8, T < 2^31 and T * F / 8 < 2^31 * 1024; out's storage range disjoint from gate_up's.  The
+    grid rule -- the work flattened over (row, 16-byte chunk of 8 outputs), a workgroup taking 1,024
+    consecutive chunks (8,192 outputs), thread t the chunks t, t + 256, t + 512, t + 768 of them:
+    ceil(T * F / 8192) workgroups -- is part of the contract (models.workloads.default_swiglu_workgroups).
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -104,7 +122,10 @@ positions and the touched table entries; it writes the same rows of q_out and, p
 head, the 128 K elements of the token's slot and its 128 V elements -- every other byte of the caches,
 the earlier slots of the chunk's first block and the slots past ctx of its last included, is
 bit-preserved, and the caches are never read.  q_len == 0 and ctx == 0 write nothing; replaying the
-launch is idempotent.
+launch is idempotent.  add_rmsnorm reads the T x D windows of x and residual and the D elements of
+weight and writes the T x D windows of out and residual_out; swiglu reads the T x 2F window of gate_up and
+writes the T x F window of out.  The padding between the rows of a strided operand is neither read nor
+written.
 
 Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
 of the conversion and float64 sums):
@@ -174,7 +195,26 @@ of the conversion and float64 sums):
     contraction setting, then one rounding to bf16 (nearest even, subnormals kept).  A NaN or Inf in
     x1, x2, c or s reaches both outputs of its pair wherever IEEE says so (0 * NaN and 0 * Inf are NaN:
     no zero is skipped) and no other element.  V is copied bit for bit, NaN payloads and -0.0
-    included.
+    included;
+  * add_rmsnorm (pinned by tests/test_gpu_rmsnorm_exact.py): h = fp32(x) + fp32(residual) is one fp32 add
+    and residual_out = bf16(h), round to nearest even.  hb = fp32(residual_out) is the ROUNDED stream and
+    the norm is computed from it, so add_rmsnorm(x, w, residual) gives bit for bit the y of
+    add_rmsnorm(residual_out, w) without a residual; without a residual hb = fp32(x) and no
+    residual_out is written.  ss = sum of hb^2 is accumulated in fp32 with fma: per-thread partials, a
+    wave butterfly, then the four wave partials summed in one fixed order by every thread -- all threads
+    of a row hold the same ss; the order is otherwise unspecified; there are no atomics, so two launches
+    on the same inputs are bit-identical.  r = 1.0f / sqrtf(ss / float(D) + eps): an IEEE division, an
+    fp32 add, a correctly rounded square root and an IEEE division (no rsqrt, no fast-math).
+    y = bf16((hb * r) * fp32(w)): two fp32 multiplies in that order and one rounding.  Non-finite values
+    and zeros are not special-cased: a NaN in a row makes that row's y all NaN and, in residual_out, only
+    its own element; an all-zero row with eps > 0 gives zeros with the sign of hb * w, with eps == 0
+    NaN (0 * Inf); no other row is ever affected;
+  * swiglu (pinned by tests/test_gpu_swiglu_exact.py): in fp32, e = exp2(-g * log2 e) -- the product
+    rounded to fp32, the hardware exponential (v_exp_f32) -- s = g / (1.0f + e), an IEEE division, and
+    out = bf16(s * u), one rounding.  So g = +-0 gives e == 1 and s = +-0; g >= 128 gives e == 0 exactly,
+    s == g and out = bf16(g * u), an exact fp32 product; g <= -128 gives e == +Inf and s = -0.0;
+    g = -Inf gives NaN, as torch.nn.functional.silu does; g = +Inf gives +-Inf * u.  A NaN or Inf in g or
+    u reaches its own output element and no other.
 """
 from __future__ import annotations
 
@@ -721,6 +761,130 @@ def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
                                block_table.data_ptr(), ctx_lens.data_ptr(), q_start.data_ptr(), q_out.data_ptr(), S, Hq,
                                Hkv, int(max_q_len), int(max_pos), ld_qkv, ld_q_out, ld_table, sp)
     return q_out
+
+
+RMSNORM_D_MIN, RMSNORM_D_MAX = 8, 8192
+
+
+def _bf16_rows(name: str, nm: str, t: torch.Tensor, cols: Optional[int] = None) -> int:
+    """The checks add_rmsnorm and swiglu make of every 2-D operand: bf16, 2-D (of `cols` columns when
+    given), last dim contiguous, a row stride >= the row length and a multiple of 8, the first element
+    16-byte aligned, fewer than 2^31 rows.  Returns the row stride in elements."""
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 tensors ({nm} is {t.dtype})")
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name}: {nm} must be 2-D" + (f" with {cols} columns" if cols is not None else "")
+                         + f" (got {tuple(t.shape)})")
+    rows, n = t.shape
+    if n > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: {nm} must have contiguous rows")
+    if rows > 1 and (t.stride(0) < n or t.stride(0) % 8):
+        raise ValueError(f"{name}: {nm} row stride {t.stride(0)} must be >= {n} and a multiple of 8")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name}: {nm} must be 16-byte aligned")
+    if rows >= 2 ** 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 rows")
+    return _row_stride(t, rows, n)
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    (a0, a1), (b0, b1) = _storage_range(a), _storage_range(b)
+    return a0 < b1 and b0 < a1
+
+
+def add_rmsnorm(x: torch.Tensor, weight: torch.Tensor, residual: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                out: Optional[torch.Tensor] = None, residual_out: Optional[torch.Tensor] = None,
+                stream: Optional[torch.cuda.Stream] = None):
+    """Residual add + RMSNorm over the rows of x [T, D] (bf16, D a multiple of 8 in [8, 8192]), weight bf16
+    [D].  With a residual [T, D]: residual_out = bf16(fp32(x) + fp32(residual)) and, from the ROUNDED sum
+    hb = fp32(residual_out), y = bf16((hb * r) * fp32(weight)) with r = 1 / sqrt(mean(hb^2) + eps) in fp32;
+    returns (y, residual_out).  Without one hb = fp32(x), nothing but y is written and y is returned:
+    add_rmsnorm(x, w, residual)[0] is bit for bit add_rmsnorm(residual_out, w).  `out` and `residual_out`
+    are made when None.  residual_out may be EXACTLY residual (same data_ptr, shape and strides): the
+    in-place update of the residual stream -- a thread reads its chunks before it writes them.  A captured
+    launch of that form is not idempotent: every replay adds x again.  Any other overlap of an output with
+    an operand or with the other output raises.  eps is finite, >= 0 and rounded to fp32 once, here.
+    T == 0 launches nothing."""
+    name = "add_rmsnorm"
+    _check_devices(name, x, weight, residual, out, residual_out)
+    if x.dim() == 2 and (x.shape[1] < RMSNORM_D_MIN or x.shape[1] > RMSNORM_D_MAX or x.shape[1] % 8):
+        raise ValueError(f"{name}: D = {x.shape[1]} must be a multiple of 8 in [{RMSNORM_D_MIN}, {RMSNORM_D_MAX}]")
+    ld_x = _bf16_rows(name, "x", x)
+    T, D = x.shape
+    if weight.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 tensors (weight is {weight.dtype})")
+    if weight.dim() != 1 or weight.numel() != D or not weight.is_contiguous() or weight.data_ptr() % 16:
+        raise ValueError(f"{name}: weight must be a contiguous, 16-byte aligned vector of length D = {D}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"{name}: eps = {eps!r} must be finite and >= 0")
+    eps32 = torch.tensor(float(eps), dtype=torch.float32).item()          # rounded to fp32 once
+    if eps32 == float("inf"):
+        raise ValueError(f"{name}: eps = {eps!r} is past the fp32 range")
+    if residual is None and residual_out is not None:
+        raise ValueError(f"{name}: residual_out without a residual")
+    ld_res = ld_ro = 0
+    if residual is not None:
+        ld_res = _bf16_rows(name, "residual", residual, D)
+        if residual.shape[0] != T:
+            raise ValueError(f"{name}: residual {tuple(residual.shape)} does not match x {tuple(x.shape)}")
+        if residual_out is None:
+            residual_out = torch.empty((T, D), dtype=torch.bfloat16, device=x.device)
+        ld_ro = _bf16_rows(name, "residual_out", residual_out, D)
+        if residual_out.shape[0] != T:
+            raise ValueError(f"{name}: residual_out {tuple(residual_out.shape)} does not match x {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty((T, D), dtype=torch.bfloat16, device=x.device)
+    ld_y = _bf16_rows(name, "out", out, D)
+    if out.shape[0] != T:
+        raise ValueError(f"{name}: out {tuple(out.shape)} does not match x {tuple(x.shape)}")
+    for nm, t in (("x", x), ("weight", weight), ("residual", residual), ("residual_out", residual_out)):
+        if t is not None and _overlap(out, t):
+            raise ValueError(f"{name}: out overlaps {nm}")
+    if residual_out is not None:
+        in_place = (residual_out.data_ptr() == residual.data_ptr() and residual_out.shape == residual.shape
+                    and residual_out.stride() == residual.stride())
+        for nm, t in (("x", x), ("weight", weight), ("residual", None if in_place else residual)):
+            if t is not None and _overlap(residual_out, t):
+                raise ValueError(f"{name}: residual_out overlaps {nm} (it may only be exactly residual)")
+    result = out if residual is None else (out, residual_out)
+    if T == 0:
+        return result
+    h = _native.hip()
+    with torch.cuda.device(x.device):
+        h.add_rmsnorm_bf16(x.data_ptr(), residual.data_ptr() if residual is not None else 0, weight.data_ptr(),
+                           residual_out.data_ptr() if residual is not None else 0, out.data_ptr(), T, D, ld_x, ld_res,
+                           ld_ro, ld_y, eps32, _stream_ptr(stream, x.device))
+    return result
+
+
+def swiglu(gate_up: torch.Tensor, out: Optional[torch.Tensor] = None,
+           stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """out[t, j] = bf16(silu(g) * u) with g = gate_up[t, j], u = gate_up[t, F + j] -- gate_up bf16 [T, 2F], the
+    output of a fused gate / up projection, out bf16 [T, F] (made when None), F a multiple of 8.  In fp32:
+    e = exp2(-g * log2 e) on the hardware exponential, s = g / (1 + e) (an IEEE division), s * u rounded to
+    bf16 once.  out may not overlap gate_up.  T == 0 launches nothing; replaying a launch gives the same."""
+    name = "swiglu"
+    _check_devices(name, gate_up, out)
+    if gate_up.dim() == 2 and (gate_up.shape[1] < 16 or gate_up.shape[1] % 16):
+        raise ValueError(f"{name}: gate_up has {gate_up.shape[1]} columns: no 2 * F with F a positive multiple of 8")
+    ld_in = _bf16_rows(name, "gate_up", gate_up)
+    T, F2 = gate_up.shape
+    F = F2 // 2
+    if T * (F // 8) >= 2 ** 31 * 1024:
+        raise ValueError(f"{name}: more than 2^31 - 1 workgroups")
+    if out is None:
+        out = torch.empty((T, F), dtype=torch.bfloat16, device=gate_up.device)
+    ld_out = _bf16_rows(name, "out", out, F)
+    if out.shape[0] != T:
+        raise ValueError(f"{name}: out {tuple(out.shape)} does not match gate_up {tuple(gate_up.shape)}")
+    if _overlap(out, gate_up):
+        raise ValueError(f"{name}: out overlaps gate_up")
+    if T == 0:
+        return out
+    h = _native.hip()
+    with torch.cuda.device(gate_up.device):
+        h.swiglu_bf16(gate_up.data_ptr(), out.data_ptr(), T, F, ld_in, ld_out, _stream_ptr(stream, gate_up.device))
+    return out
 
 
 def gemm_flops(M: int, N: int, K: int) -> float:

@@ -148,6 +148,23 @@ def _rope_append_operands(o: Op, g: torch.Generator, device: torch.device) -> tu
     return q_out, qkv, cos_sin, kc, vc, table, ctx, q_start
 
 
+def _add_rmsnorm_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(y, res_out, x, residual, weight): M rows of N elements; x and residual are randn, the weight is
+    1 + 0.1 * randn, all bf16.  The outputs are buffers of their own (the launch is replayable)."""
+    x = torch.randn(o.M, o.N, generator=g).to(torch.bfloat16).to(device)
+    residual = torch.randn(o.M, o.N, generator=g).to(torch.bfloat16).to(device)
+    weight = (1 + 0.1 * torch.randn(o.N, generator=g)).to(torch.bfloat16).to(device)
+    y = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
+    res_out = torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device)
+    return y, res_out, x, residual, weight
+
+
+def _swiglu_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, gate_up): M rows of N gate and N up columns, randn in bf16."""
+    gate_up = torch.randn(o.M, 2 * o.N, generator=g).to(torch.bfloat16).to(device)
+    return torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device), gate_up
+
+
 def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return tuple(torch.ones(o.n_floats, dtype=torch.float32, device=device) for _ in range(3))
 
@@ -191,6 +208,16 @@ def _launch_rope_append(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.rope_append(qkv, cos_sin, kc, vc, table, ctx, q_start, max_q_len=o.q, q_out=q_out, stream=st, check=False)
 
 
+def _launch_add_rmsnorm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    y, res_out, x, residual, weight = t
+    loadgen.add_rmsnorm(x, weight, residual, out=y, residual_out=res_out, stream=st)
+
+
+def _launch_swiglu(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, gate_up = t
+    loadgen.swiglu(gate_up, out=out, stream=st)
+
+
 def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     x, y, z = t
     loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
@@ -201,7 +228,7 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # position of the output in the tuple).  Operand layouts: GEMMs (a, bt, bias, c); gather (out,
 # table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); prefill the same and q_start;
 # attn_split the same and the workspace; rope_append (q_out, qkv, cos_sin, k_cache, v_cache, table, ctx,
-# q_start); triad (x, y, z), x = y + s z.
+# q_start); add_rmsnorm (y, res_out, x, residual, weight); swiglu (out, gate_up); triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -210,6 +237,8 @@ OP_KINDS = {
     "attn_split": (_attn_split_operands, _launch_attn_split, 0),
     "prefill": (_prefill_operands, _launch_prefill, 0),
     "rope_append": (_rope_append_operands, _launch_rope_append, 0),
+    "add_rmsnorm": (_add_rmsnorm_operands, _launch_add_rmsnorm, 0),
+    "swiglu": (_swiglu_operands, _launch_swiglu, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -75,6 +75,21 @@ void rope_append_bf16(uintptr_t qkv, uintptr_t cos_sin, uintptr_t k_cache, uintp
 // workgroups of that launch: one per (sequence, KV head, cache block a chunk of max_q_len tokens can touch):
 // S * Hkv * ((max_q_len + 30) / 32 + 1), 0 where S == 0 or max_q_len == 0
 int rope_append_workgroups(int S, int Hkv, int max_q_len);
+// Residual add + RMSNorm -- native/hip/rmsnorm.hip: x, residual, res_out, y bf16 [T, D] with row strides (in elements),
+// weight bf16 [D], D a multiple of 8 in [8, 8192].  res_out = bf16(x + residual); y = bf16((hb * r) * weight) with
+// hb = fp32(res_out) and r = 1 / sqrt(mean(hb^2) + eps).  residual == 0: none -- hb = fp32(x), res_out (0 too) is not
+// written.  res_out may be exactly residual; nothing else may overlap an output
+void add_rmsnorm_bf16(uintptr_t x, uintptr_t residual /*0: none*/, uintptr_t weight, uintptr_t res_out, uintptr_t y,
+                      int T, int D, int64_t ld_x, int64_t ld_res, int64_t ld_res_out, int64_t ld_y, float eps,
+                      uintptr_t stream);
+// workgroups of that launch: one per row
+int add_rmsnorm_workgroups(int T);
+// SwiGLU -- native/hip/swiglu.hip: gate_up bf16 [T, 2F] (gate columns [0, F), up columns [F, 2F)), out bf16 [T, F],
+// F a multiple of 8, row strides in elements: out = bf16(g / (1 + exp2(-g * log2e)) * u)
+void swiglu_bf16(uintptr_t gate_up, uintptr_t out, int T, int F, int64_t ld_in, int64_t ld_out, uintptr_t stream);
+// workgroups of that launch: one per 1,024 16-byte output chunks of the flattened (row, chunk) space,
+// ceil(T * F / 8192)
+int swiglu_workgroups(int T, int F);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

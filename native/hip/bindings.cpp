@@ -92,6 +92,14 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("S"), py::arg("Hq"), py::arg("Hkv"), py::arg("max_q_len"), py::arg("max_pos"), py::arg("ld_qkv"),
         py::arg("ld_q_out"), py::arg("ld_table"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
   m.def("rope_append_workgroups", &gs::rope_append_workgroups, py::arg("S"), py::arg("Hkv"), py::arg("max_q_len"));
+  m.def("add_rmsnorm_bf16", &gs::add_rmsnorm_bf16, py::arg("x"), py::arg("residual"), py::arg("weight"),
+        py::arg("res_out"), py::arg("y"), py::arg("T"), py::arg("D"), py::arg("ld_x"), py::arg("ld_res"),
+        py::arg("ld_res_out"), py::arg("ld_y"), py::arg("eps"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("add_rmsnorm_workgroups", &gs::add_rmsnorm_workgroups, py::arg("T"));
+  m.def("swiglu_bf16", &gs::swiglu_bf16, py::arg("gate_up"), py::arg("out"), py::arg("T"), py::arg("F"),
+        py::arg("ld_in"), py::arg("ld_out"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("swiglu_workgroups", &gs::swiglu_workgroups, py::arg("T"), py::arg("F"));
   // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once
   for (int k = 0; k < gs::kNumKnobs; ++k)
     m.def(("set_" + std::string(gs::kKnobs[k].name)).c_str(), [k](int value) { gs::set_knob(gs::Knob(k), value); });
