@@ -139,7 +139,8 @@ class Op:
 
     def workgroups(self, cu_budget: int) -> Optional[int]:
         """Workgroups of the op's launch under the default kernel policy (GEMM tiles picked for
-        `cu_budget` CUs, 0 = the whole chip); None: the stream kernel's 8192 blocks fill any chip."""
+        `cu_budget` CUs, 0 = the whole chip); None: the stream kernel's grid (one 1024-thread workgroup per 2048 float4, at most
+        8192: 2048 to 8192 for the catalog's arrays) fills any chip."""
         if self.is_gemm:
             return default_gemm_workgroups(self.M, self.N, self.K, cu_budget, self.kind == "gemm8")
         if self.kind == "gather":
@@ -494,7 +495,7 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups,
     default_attn_split_workgroups, default_prefill_workgroups and default_rope_append_workgroups count
     them, the norm's one workgroup per row (default_add_rmsnorm_workgroups) and the SwiGLU's one per 8,192
-    outputs (default_swiglu_workgroups), the stream kernels' 8192 blocks fill the chip.  A pod that leaves CUs idle alone leaves
+    outputs (default_swiglu_workgroups), the stream kernels' grids fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
     t = f = 0.0

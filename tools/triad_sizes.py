@@ -1,5 +1,5 @@
-"""Lone stream-triad bandwidth per working-set size for the non-temporal (3) and write-through
-(8) store variants: the bench's triads stream 3 x 64 / 128 / 256 MiB (batch 1024 / 2048 / 4096),
+"""Lone stream-triad bandwidth per working-set size for the triad variants given as arguments (default: the
+non-temporal (3) and write-through (8) store variants): the bench's triads stream 3 x 64 / 128 / 256 MiB (batch 1024 / 2048 / 4096),
 the smaller ones within reach of the 256 MiB Infinity Cache across a pod's 20 iterations."""
 import json
 import os
@@ -16,11 +16,12 @@ from k8s_gpu_scheduler_amd.ops import loadgen  # noqa: E402
 
 def main() -> None:
     h = _native.hip(required=True)
+    variants = [int(v) for v in sys.argv[1:]] or [3, 8]         # e.g. `triad_sizes.py 3 5 7`
     res = []
     for n in (16 << 20, 32 << 20, 64 << 20):
         x, y, z = (torch.ones(n, device="cuda") for _ in range(3))
         for rnd in range(2):
-            for v in (3, 8):
+            for v in variants:
                 h.set_triad_variant(v)
                 for _ in range(3):
                     loadgen.triad(x, y, z, 1.0001)
