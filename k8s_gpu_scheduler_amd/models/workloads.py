@@ -42,6 +42,11 @@ two bf16 streams in, two out, a cross-lane and cross-wave sum per row, no MFMA w
 A ninth is "swiglu" (LLM_BLOCK), silu(gate) * up between the fused gate / up projection and the down projection
 (ops.loadgen.swiglu): an element-wise stream like the triad, but bf16, pairing column j with column F + j of the
 same row, and with a transcendental and an IEEE division -- about 20 VALU operations -- per 6 bytes.
+A tenth is "sample" (LLM_HEAD), top-k / top-p token sampling from the LM head's logits (ops.loadgen.sample_tokens):
+one very long row per sequence (128,256 bf16 logits = 250 KiB) read once into the registers of one workgroup, an
+exact selection of its k largest elements through an LDS histogram of 16-bit order keys, a short sorted softmax
+over the survivors and a 4-byte result -- integer compares and LDS atomics, no MFMA work, one exponential per
+candidate.
 """
 from __future__ import annotations
 
@@ -64,11 +69,12 @@ class Op:
     #                        | "rope_append" (bf16 RoPE of q and K and the append of the new K / V to the same cache)
     #                        | "add_rmsnorm" (bf16 residual add + RMSNorm of M rows of N elements, always with a residual)
     #                        | "swiglu" (bf16 silu(gate) * up: M rows of 2 N in, M rows of N out)
-    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu: rows
+    #                        | "sample" (top-k / top-p token sampling: M rows of N bf16 logits in, M int32 tokens out)
+    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu, sample: rows
     N: int = 0             # gather: D, the row length; attn, attn_split, prefill, rope_append: query heads;
-    #                        add_rmsnorm: D, the row length; swiglu: F, the output row length
+    #                        add_rmsnorm: D, the row length; swiglu: F, the output row length; sample: V, the vocabulary
     K: int = 0             # gather: pooling factor (rows per bag); attn, attn_split, prefill, rope_append: context tokens
-    #                        per sequence (rope_append: the chunk included)
+    #                        per sequence (rope_append: the chunk included); sample: the top-k (1 .. 64)
     relu: bool = True
     n_floats: int = 0      # triad
     rows: int = 0          # gather: rows of the table; attn, attn_split, prefill, rope_append: KV heads
@@ -99,6 +105,8 @@ class Op:
             return 5.0 * self.M * self.N
         if self.kind == "swiglu":                                 # two multiplies, the exp as one, an add, a division, a multiply
             return 6.0 * self.M * self.N
+        if self.kind == "sample":                                 # the maximum's compare and the selection's compare per logit
+            return 2.0 * self.M * self.N
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -131,6 +139,8 @@ class Op:
             return 8.0 * self.M * self.N + 2.0 * self.N
         if self.kind == "swiglu":                                 # gate and up read, out written
             return 6.0 * self.M * self.N
+        if self.kind == "sample":                                 # the logits once, four parameter words and the token per row
+            return 2.0 * self.M * self.N + 20.0 * self.M
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -157,6 +167,8 @@ class Op:
             return default_add_rmsnorm_workgroups(self.M)
         if self.kind == "swiglu":
             return default_swiglu_workgroups(self.M, self.N)
+        if self.kind == "sample":
+            return default_sample_workgroups(self.M)
         return None
 
 
@@ -335,9 +347,36 @@ LLM_BLOCK: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "sample" kind, which those pinned tables do not list either: the TAIL of a decode step for
+# Llama-3's vocabulary of 128,256 tokens -- the final residual add + RMSNorm, the LM-head projection onto the
+# vocabulary (no ReLU, 1 GiB of bf16 weights streamed for a few rows: HBM-bound, 501 column tiles of 256 or
+# 1,002 of 128), top-k / top-p sampling of the next token from the logits (top_k = 50).  Each op keeps its own
+# operands, as everywhere in the executor.
+#   llm_head_decode_256  behind llm_block_decode_256: 256 rows, so the sampler is 256 workgroups, one per CU,
+#                        reading 64 MB of logits
+#   llm_head_decode_8    behind llm_decode_long_8: the 8 new tokens ride in the GEMMs' minimum 64-row tile (the
+#                        norm and the projection run 64 rows, 56 of them padding), and the sampler takes the 8
+#                        real rows: 8 workgroups on 256 CUs.  That is the case a split-row launch (several
+#                        workgroups per row and a merge, like the split-KV attention) would address; it is out
+#                        of scope here
+# The sampler is a tenth kernel character; no co-run groups are measured with it yet
+_HEAD_D, _HEAD_V, _HEAD_TOP_K = 4096, 128256, 50
+
+
+def _llm_head(rows: int, seqs: int) -> Tuple[Op, ...]:
+    return (Op("add_rmsnorm", rows, _HEAD_D), Op("gemm", rows, _HEAD_V, _HEAD_D, relu=False),
+            Op("sample", seqs, _HEAD_V, _HEAD_TOP_K))
+
+
+LLM_HEAD: Dict[str, Workload] = {
+    "llm_head_decode_256": Workload("llm_head_decode_256", "llm_head_decode", "hip", 256, _llm_head(256, 256), 1.25),
+    "llm_head_decode_8": Workload("llm_head_decode_8", "llm_head_decode_few", "hip", 8, _llm_head(64, 8), 1.0),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra, staged, long-context, LLM-layer or LLM-block workload by exact name."""
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK):
+    """A catalog, extra, staged, long-context, LLM-layer, LLM-block or LLM-head workload by exact name."""
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD):
         w = table.get(name)
         if w is not None:
             return w
@@ -348,9 +387,9 @@ def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
     the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones, the LLM-block
-    ones last."""
+    ones, the LLM-head ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK):
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -488,6 +527,12 @@ def default_swiglu_workgroups(T: int, F: int) -> int:
     return -(-(T * (F // 8)) // SWIGLU_CHUNKS_PER_WORKGROUP)
 
 
+def default_sample_workgroups(S: int) -> int:
+    """Workgroups the native token-sampling launch gets: one per row of logits -- a pure-Python copy of
+    sample_workgroups (native/hip/sample.hip), pinned against it in tests/test_sample_cpu.py."""
+    return S
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
@@ -495,7 +540,8 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups,
     default_attn_split_workgroups, default_prefill_workgroups and default_rope_append_workgroups count
     them, the norm's one workgroup per row (default_add_rmsnorm_workgroups) and the SwiGLU's one per 8,192
-    outputs (default_swiglu_workgroups), the stream kernels' grids fill the chip.  A pod that leaves CUs idle alone leaves
+    outputs (default_swiglu_workgroups), the sampler's one per row of logits (default_sample_workgroups), the
+    stream kernels' grids fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
     t = f = 0.0

@@ -1,6 +1,7 @@
 """Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
-native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip).
+native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip,
+native/hip/sample.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
@@ -14,7 +15,10 @@ block_table, ctx_lens, q_start)` rotates q and K (RoPE) and appends the new K / 
 latency-dominated, write-scattering); `add_rmsnorm(x, weight, residual)` is the residual add + RMSNorm in
 front of a decoder block's projections (a row reduction and a second pass over the same row, two bf16
 streams in and two out) and `swiglu(gate_up)` the activation between its fused gate / up and down
-projections (an element-wise bf16 stream with an exponential and an IEEE division per element).  Shapes are validated on the host before launch (the kernels
+projections (an element-wise bf16 stream with an exponential and an IEEE division per element);
+`sample_tokens(logits, u, temperature, top_k, top_p)` picks the next token of every sequence from the LM
+head's logits (top-k / top-p sampling: one very long row per sequence, an exact selection, a short sorted
+softmax, a 4-byte result; the caller supplies the uniforms).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
@@ -100,7 +104,15 @@ kernels) rely on:
     multiple of 8, T < 2^31 and T * F / 8 < 2^31 * 1024; out's storage range disjoint from gate_up's.  The
     grid rule -- the work flattened over (row, 16-byte chunk of 8 outputs), a workgroup taking 1,024
     consecutive chunks (8,192 outputs), thread t the chunks t, t + 256, t + 512, t + 768 of them:
-    ceil(T * F / 8192) workgroups -- is part of the contract (models.workloads.default_swiglu_workgroups).
+    ceil(T * F / 8192) workgroups -- is part of the contract (models.workloads.default_swiglu_workgroups);
+  * sample_tokens (native/hip/sample.hip): logits bf16 [S, V], 2-D with contiguous rows, a row stride >= V and
+    a multiple of 8, the first element 16-byte aligned; V a multiple of 8 in [8, 131072] (a thread keeps at
+    most 16 chunks of its row in registers), S < 2^31; u, temperature and top_p fp32 [S], top_k int32 [S],
+    each 1-D and contiguous; out int32 [S], contiguous, its storage range disjoint from every input's.  The
+    kernel trusts the parameters, except that it clamps top_k into [1, 64] itself: check=True verifies
+    1 <= top_k <= 64, temperature finite and >= 0 and, on the rows that are not greedy (temperature == 0 or
+    top_k == 1), 0 < top_p <= 1 and 0 <= u < 1, on the device first (one sync); check=False never syncs.
+    One workgroup per row (models.workloads.default_sample_workgroups).
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -124,8 +136,9 @@ the earlier slots of the chunk's first block and the slots past ctx of its last 
 bit-preserved, and the caches are never read.  q_len == 0 and ctx == 0 write nothing; replaying the
 launch is idempotent.  add_rmsnorm reads the T x D windows of x and residual and the D elements of
 weight and writes the T x D windows of out and residual_out; swiglu reads the T x 2F window of gate_up and
-writes the T x F window of out.  The padding between the rows of a strided operand is neither read nor
-written.
+writes the T x F window of out.  sample_tokens reads the S x V window of logits and the S elements of u,
+temperature, top_k and top_p and writes the S elements of out.  The padding between the rows of a strided
+operand is neither read nor written.
 
 Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
 of the conversion and float64 sums):
@@ -214,7 +227,39 @@ of the conversion and float64 sums):
     out = bf16(s * u), one rounding.  So g = +-0 gives e == 1 and s = +-0; g >= 128 gives e == 0 exactly,
     s == g and out = bf16(g * u), an exact fp32 product; g <= -128 gives e == +Inf and s = -0.0;
     g = -Inf gives NaN, as torch.nn.functional.silu does; g = +Inf gives +-Inf * u.  A NaN or Inf in g or
-    u reaches its own output element and no other.
+    u reaches its own output element and no other;
+  * sample_tokens (pinned by tests/test_gpu_sample_exact.py).  Row-level rules:
+      - Comparisons are on values: +0.0 == -0.0.
+      - A row that holds any NaN, or whose maximum is -Inf, gives token -1.  No other row is affected.
+      - A row whose maximum is +Inf gives the lowest index holding +Inf, in either mode.
+      - Greedy (temperature == 0 or top_k == 1): the token is the lowest index of the row maximum.  No
+        exponential is computed.  u and top_p are not read as numbers and may be NaN.
+    Candidates:
+      - k = min(clamp(top_k, 1, 64), V).
+      - The candidates are the k largest logits.  Ties at the threshold value go to the lowest indices.
+      - They are ranked c_0 .. c_{k-1} by (value descending, index ascending).
+      - The kernel itself clamps top_k into [1, 64].  This is one v_med3, and an out-of-range value must not
+        be able to run past the LDS candidate array.
+    Weights:
+      - c = 1.44269504f / temperature is an IEEE division.
+      - a_j = (l_{c_j} - l_{c_0}) * c is one fp32 subtraction and one fp32 multiply.
+      - w_j is the hardware exp2 (v_exp_f32) of a_j, as in swiglu.hip and the attentions.
+      - Consequences: w_0 == 1 exactly; equal logits give exactly 1; a_j <= -150 (and -Inf) gives exactly 0.
+    Cumulative sum:
+      - cum_j is the inclusive fp32 prefix sum of w in rank order.
+      - The association is unspecified but fixed (a wave scan).
+      - There are no float atomics, so two launches on the same inputs give identical tokens.
+      - Z = cum_{k-1}.
+    Top-p:
+      - n is the smallest n >= 1 with cum_{n-1} >= top_p * Z (one fp32 multiply).
+      - top_p == 1 keeps all k.
+    Pick:
+      - target = u * cum_{n-1}.
+      - The token is c_j for the smallest j < n with cum_j > target.
+      - If no such j exists, the token is c_{n-1}.
+    Memory:
+      - Nothing outside the S x V window and the five [S] vectors is read.
+      - Only out[0..S) is written.
 """
 from __future__ import annotations
 
@@ -884,6 +929,77 @@ def swiglu(gate_up: torch.Tensor, out: Optional[torch.Tensor] = None,
     h = _native.hip()
     with torch.cuda.device(gate_up.device):
         h.swiglu_bf16(gate_up.data_ptr(), out.data_ptr(), T, F, ld_in, ld_out, _stream_ptr(stream, gate_up.device))
+    return out
+
+
+SAMPLE_V_MIN, SAMPLE_V_MAX = 8, 131072
+SAMPLE_MAX_TOP_K = 64
+
+
+def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
+                  top_p: torch.Tensor, out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                  check: bool = True) -> torch.Tensor:
+    """Top-k / top-p sampling of one token per row of logits bf16 [S, V] (V a multiple of 8 in [8, 131072]);
+    returns out, int32 [S] (made when None).  Per row s, with the parameters temperature[s] (fp32), top_k[s]
+    (int32), top_p[s] (fp32) and the caller's uniform u[s] (fp32, in [0, 1): there is no RNG in the kernel, so a
+    replayed launch gives the same): the k = min(clamp(top_k, 1, 64), V) largest logits, ties at the threshold
+    to the lowest indices, ranked c_0 .. c_{k-1} by (value descending, index ascending); in fp32
+    w_j = exp2((l_{c_j} - l_{c_0}) * (1.44269504f / temperature)) on the hardware exponential, cum the
+    inclusive prefix sum of w; n the smallest n >= 1 with cum_{n-1} >= top_p * cum_{k-1}; the token is c_j for
+    the smallest j < n with cum_j > u * cum_{n-1}, c_{n-1} if there is none.  temperature == 0 or top_k == 1 is
+    greedy: the lowest index of the row maximum, u and top_p unused (they may be NaN).  A row with a NaN, or
+    whose maximum is -Inf, gives -1; a maximum of +Inf gives its lowest index; no other row is affected.
+    check=True verifies on the device first (one sync): 1 <= top_k <= 64, temperature finite and >= 0, and on
+    the rows that are not greedy 0 < top_p <= 1 and 0 <= u < 1.  check=False never syncs (the kernel still
+    clamps top_k into [1, 64]): for callers that guarantee the parameters, and under graph capture.
+    S == 0 launches nothing."""
+    name = "sample_tokens"
+    _check_devices(name, logits, u, temperature, top_k, top_p, out)
+    if logits.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 logits (got {logits.dtype})")
+    for nm, t in (("u", u), ("temperature", temperature), ("top_p", top_p)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} expects an fp32 {nm} (got {t.dtype})")
+    if top_k.dtype != torch.int32:
+        raise TypeError(f"{name} expects an int32 top_k (got {top_k.dtype})")
+    if out is not None and out.dtype != torch.int32:
+        raise TypeError(f"{name} expects an int32 out (got {out.dtype})")
+    ld = _bf16_rows(name, "logits", logits)
+    S, V = logits.shape
+    if V < SAMPLE_V_MIN or V > SAMPLE_V_MAX or V % 8:
+        raise ValueError(f"{name}: V = {V} must be a multiple of 8 in [{SAMPLE_V_MIN}, {SAMPLE_V_MAX}]")
+    for nm, t in (("u", u), ("temperature", temperature), ("top_k", top_k), ("top_p", top_p)):
+        if t.dim() != 1 or t.numel() != S or not t.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be a contiguous vector of length S = {S} (got {tuple(t.shape)})")
+    if out is None:
+        out = torch.empty(S, dtype=torch.int32, device=logits.device)
+    if out.dim() != 1 or out.numel() != S or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous vector of length S = {S} (got {tuple(out.shape)})")
+    for nm, t in (("logits", logits), ("u", u), ("temperature", temperature), ("top_k", top_k), ("top_p", top_p)):
+        if _overlap(out, t):
+            raise ValueError(f"{name}: out overlaps {nm}")
+    if S == 0:
+        return out
+    h = _native.hip()
+    with torch.cuda.device(logits.device):
+        sp = _stream_ptr(stream, logits.device)
+        if check:
+            with _launch_stream(stream, logits.device):
+                sampled = (temperature != 0) & (top_k != 1)
+                bad = torch.stack([((top_k < 1) | (top_k > SAMPLE_MAX_TOP_K)).any(),
+                                   (~torch.isfinite(temperature) | (temperature < 0)).any(),
+                                   (~((top_p > 0) & (top_p <= 1)) & sampled).any(),
+                                   (~((u >= 0) & (u < 1)) & sampled).any()]).tolist()          # the one sync
+            if bad[0]:
+                raise ValueError(f"{name}: a top_k is outside [1, {SAMPLE_MAX_TOP_K}]")
+            if bad[1]:
+                raise ValueError(f"{name}: a temperature is negative or not finite")
+            if bad[2]:
+                raise ValueError(f"{name}: a top_p of a sampled row is outside (0, 1]")
+            if bad[3]:
+                raise ValueError(f"{name}: a u of a sampled row is outside [0, 1)")
+        h.sample_topk_bf16(logits.data_ptr(), u.data_ptr(), temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
+                           out.data_ptr(), S, V, ld, sp)
     return out
 
 

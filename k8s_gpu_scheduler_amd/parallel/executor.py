@@ -165,13 +165,30 @@ def _swiglu_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device), gate_up
 
 
+SAMPLE_TEMPERATURE, SAMPLE_TOP_P = 0.8, 0.9          # the "sample" op's parameters, the same on every row
+
+
+def _sample_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, logits, u, temperature, top_k, top_p): M rows of N logits, bf16(1.5 * randn); u is rand, the
+    temperature 0.8, top_k = o.K and top_p 0.9 on every row.  The per-row u is drawn before the logits
+    (tests/test_sample_cpu.py counts how many rows of the two LLM-head workloads put u or top_p close to a
+    boundary of the cumulative weights)."""
+    u = torch.rand(o.M, generator=g).to(device)
+    logits = (1.5 * torch.randn(o.M, o.N, generator=g)).to(torch.bfloat16).to(device)
+    temperature = torch.full((o.M,), SAMPLE_TEMPERATURE, dtype=torch.float32, device=device)
+    top_k = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
+    top_p = torch.full((o.M,), SAMPLE_TOP_P, dtype=torch.float32, device=device)
+    return torch.empty(o.M, dtype=torch.int32, device=device), logits, u, temperature, top_k, top_p
+
+
 def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return tuple(torch.ones(o.n_floats, dtype=torch.float32, device=device) for _ in range(3))
 
 
 # The launches look their loadgen entry point up when called (tests replace the attributes).  The
 # gather's indices, and the attention's ctx_lens and block ids, are in range by construction: no
-# check, no sync (this runs under graph capture); so are the prefill's q_start and max_q_len.
+# check, no sync (this runs under graph capture); so are the prefill's q_start and max_q_len, and the
+# sampler's parameters.
 def _launch_gemm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     a, bt, bias, c = t
     loadgen.gemm(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
@@ -218,6 +235,11 @@ def _launch_swiglu(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.swiglu(gate_up, out=out, stream=st)
 
 
+def _launch_sample(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, logits, u, temperature, top_k, top_p = t
+    loadgen.sample_tokens(logits, u, temperature, top_k, top_p, out=out, stream=st, check=False)
+
+
 def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     x, y, z = t
     loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
@@ -228,7 +250,8 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # position of the output in the tuple).  Operand layouts: GEMMs (a, bt, bias, c); gather (out,
 # table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); prefill the same and q_start;
 # attn_split the same and the workspace; rope_append (q_out, qkv, cos_sin, k_cache, v_cache, table, ctx,
-# q_start); add_rmsnorm (y, res_out, x, residual, weight); swiglu (out, gate_up); triad (x, y, z), x = y + s z.
+# q_start); add_rmsnorm (y, res_out, x, residual, weight); swiglu (out, gate_up); sample (out, logits, u,
+# temperature, top_k, top_p); triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -239,6 +262,7 @@ OP_KINDS = {
     "rope_append": (_rope_append_operands, _launch_rope_append, 0),
     "add_rmsnorm": (_add_rmsnorm_operands, _launch_add_rmsnorm, 0),
     "swiglu": (_swiglu_operands, _launch_swiglu, 0),
+    "sample": (_sample_operands, _launch_sample, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -90,6 +90,16 @@ void swiglu_bf16(uintptr_t gate_up, uintptr_t out, int T, int F, int64_t ld_in, 
 // workgroups of that launch: one per 1,024 16-byte output chunks of the flattened (row, chunk) space,
 // ceil(T * F / 8192)
 int swiglu_workgroups(int T, int F);
+// Top-k / top-p token sampling -- native/hip/sample.hip: logits bf16 [S, V] (row stride ld_logits in elements), V a
+// multiple of 8 in [8, 131072]; u, temperature, top_p fp32 [S], top_k int32 [S], out int32 [S].  Per row: the
+// k = min(clamp(top_k, 1, 64), V) largest logits (ties to the lowest indices) ranked by (value descending, index
+// ascending), weights exp2((l - l_max) * (1.44269504f / temperature)), a cut at top_p of their sum and the pick at u
+// of what is kept; temperature == 0 or top_k == 1 is the lowest index of the maximum; a NaN in the row, or a
+// maximum of -Inf, gives -1.  u holds the caller's uniforms in [0, 1): the kernel has no RNG
+void sample_topk_bf16(uintptr_t logits, uintptr_t u, uintptr_t temperature, uintptr_t top_k, uintptr_t top_p,
+                      uintptr_t out, int S, int V, int64_t ld_logits, uintptr_t stream);
+// workgroups of that launch: one per row
+int sample_workgroups(int S);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

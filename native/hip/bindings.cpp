@@ -100,6 +100,10 @@ PYBIND11_MODULE(_hip, m) {
   m.def("swiglu_bf16", &gs::swiglu_bf16, py::arg("gate_up"), py::arg("out"), py::arg("T"), py::arg("F"),
         py::arg("ld_in"), py::arg("ld_out"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
   m.def("swiglu_workgroups", &gs::swiglu_workgroups, py::arg("T"), py::arg("F"));
+  m.def("sample_topk_bf16", &gs::sample_topk_bf16, py::arg("logits"), py::arg("u"), py::arg("temperature"),
+        py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("S"), py::arg("V"), py::arg("ld_logits"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("sample_workgroups", &gs::sample_workgroups, py::arg("S"));
   // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once
   for (int k = 0; k < gs::kNumKnobs; ++k)
     m.def(("set_" + std::string(gs::kKnobs[k].name)).c_str(), [k](int value) { gs::set_knob(gs::Knob(k), value); });
