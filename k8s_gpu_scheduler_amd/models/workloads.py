@@ -47,6 +47,16 @@ one very long row per sequence (128,256 bf16 logits = 250 KiB) read once into th
 exact selection of its k largest elements through an LDS histogram of 16-bit order keys, a short sorted softmax
 over the survivors and a 4-byte result -- integer compares and LDS atomics, no MFMA work, one exponential per
 candidate.
+An eleventh is "moe_route" (LLM_MOE), the router of a mixture-of-experts MLP (ops.loadgen.moe_route): a tiny top-k
+softmax over E <= 256 logits per token -- one wave per token, integer compares, k exponentials -- and a counting sort
+of the T * k (token, choice) slots by expert in ONE workgroup, latency-bound and all but invisible to the CUs.
+A twelfth is "moe_gemm" (LLM_MOE), the grouped expert GEMM (ops.loadgen.moe_gemm): MFMA work like "gemm", but over
+ragged, data-dependent groups of token rows, one weight matrix per 64-row tile.  At decode batch sizes every expert's
+weights are streamed for about 16 rows each, so it is bound by HBM weight traffic, not by the matrix cores; the grid is
+sized for the worst routing and the fraction of its workgroups that do work is decided on the device by the router.
+A thirteenth is "moe_combine" (LLM_MOE), the weighted scatter-back of the experts' outputs to token order
+(ops.loadgen.moe_combine): k indexed 16-byte-chunked row reads and k fused multiply-adds per output chunk -- a gather
+like the embedding bag's, but weighted, over rows the same step just wrote, no MFMA work.
 """
 from __future__ import annotations
 
@@ -58,6 +68,20 @@ ATTN_HEAD_DIM = 128               # the attention kernels' head dim ...
 ATTN_BLOCK_TOKENS = 32            # ... and KV-cache block size (native/hip/decode_attn.hip, prefill_attn.hip)
 ATTN_MAX_KV_SPLITS = 32           # the split-KV decode attention: most workgroups per (sequence, KV head) ...
 ATTN_PARTIAL_FLOATS = 132         # ... and fp32 per (sequence, head, split) in its workspace: O, m, l, 2 unused
+MOE_BLOCK_M = 64                  # rows of a tile of the MoE kernels' sorted layout (native/hip/moe_gemm.hip) ...
+MOE_MAX_EXPERTS = 256             # ... the most experts ...
+MOE_MAX_TOP_K = 8                 # ... the most choices per token ...
+MOE_MAX_SLOTS = 32768             # ... and the most (token, choice) slots T * k of one routing (native/hip/moe_route.hip)
+
+
+def moe_max_tiles(T: int, k: int, E: int) -> int:
+    """The 64-row tiles the sorted MoE layout can need for T tokens, top-k k and E experts: the least upper bound on
+    sum_e ceil(c_e / 64) over all expert counts c_e >= 0 with sum c_e = T * k -- every slot its own tile, or every
+    expert with 63 rows of padding: min(T k, (T k + 63 E) // 64).  The layout's arrays and the grouped GEMM's grid
+    are sized by it on the host -- a pure-Python copy of moe_max_tiles (native/hip/moe_route.hip), pinned against it
+    in tests/test_moe_cpu.py."""
+    n = T * k
+    return min(n, (n + (MOE_BLOCK_M - 1) * E) // MOE_BLOCK_M)
 
 
 @dataclass(frozen=True)
@@ -70,16 +94,26 @@ class Op:
     #                        | "add_rmsnorm" (bf16 residual add + RMSNorm of M rows of N elements, always with a residual)
     #                        | "swiglu" (bf16 silu(gate) * up: M rows of 2 N in, M rows of N out)
     #                        | "sample" (top-k / top-p token sampling: M rows of N bf16 logits in, M int32 tokens out)
-    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu, sample: rows
+    #                        | "moe_route" (MoE routing: top-k softmax of M tokens' N expert logits, the sorted tile layout)
+    #                        | "moe_gemm" (bf16 grouped expert GEMM: the M * q routed rows times [N, K] weights of `rows` experts)
+    #                        | "moe_combine" (bf16 weighted sum of each token's K expert output rows of N elements)
+    M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu, sample: rows;
+    #                        moe_route, moe_gemm, moe_combine: T, the tokens
     N: int = 0             # gather: D, the row length; attn, attn_split, prefill, rope_append: query heads;
-    #                        add_rmsnorm: D, the row length; swiglu: F, the output row length; sample: V, the vocabulary
+    #                        add_rmsnorm: D, the row length; swiglu: F, the output row length; sample: V, the vocabulary;
+    #                        moe_route: E, the experts; moe_gemm: the output width; moe_combine: D, the row length
     K: int = 0             # gather: pooling factor (rows per bag); attn, attn_split, prefill, rope_append: context tokens
-    #                        per sequence (rope_append: the chunk included); sample: the top-k (1 .. 64)
+    #                        per sequence (rope_append: the chunk included); sample: the top-k (1 .. 64);
+    #                        moe_route, moe_combine: k, the top-k (1 .. 8); moe_gemm: the reduction length
     relu: bool = True
     n_floats: int = 0      # triad
-    rows: int = 0          # gather: rows of the table; attn, attn_split, prefill, rope_append: KV heads
-    q: int = 0             # prefill, rope_append: chunk tokens per sequence (the last q of the K context tokens; 1: decode)
+    rows: int = 0          # gather: rows of the table; attn, attn_split, prefill, rope_append: KV heads;
+    #                        moe_gemm, moe_combine: E, the experts
+    q: int = 0             # prefill, rope_append: chunk tokens per sequence (the last q of the K context tokens; 1: decode);
+    #                        moe_gemm: k, the top-k
     splits: int = 0        # attn_split: kv_splits, workgroups per (sequence, KV head)
+    gather: bool = False   # moe_gemm: A is the [T, K] token rows read through the permutation (the first projection);
+    #                        False: A is the sorted [P_max, K] intermediate read in place (the down projection)
 
     @property
     def is_gemm(self) -> bool:
@@ -88,7 +122,7 @@ class Op:
     @property
     def on_mfma(self) -> bool:
         """MFMA work in the roofline: costed max(flops term, bytes term), its flops on the MFMA side."""
-        return self.is_gemm or self.kind == "prefill"
+        return self.is_gemm or self.kind in ("prefill", "moe_gemm")
 
     @property
     def flops(self) -> float:
@@ -107,6 +141,12 @@ class Op:
             return 6.0 * self.M * self.N
         if self.kind == "sample":                                 # the maximum's compare and the selection's compare per logit
             return 2.0 * self.M * self.N
+        if self.kind == "moe_route":                              # a compare per logit in each of the k selection rounds
+            return 1.0 * self.M * self.N * self.K
+        if self.kind == "moe_gemm":                               # the T * k useful rows (pad rows and unused tiles are not work)
+            return 2.0 * self.M * self.q * self.N * self.K
+        if self.kind == "moe_combine":                            # a multiply-add per (token, choice, element)
+            return 2.0 * self.M * self.K * self.N
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -141,6 +181,15 @@ class Op:
             return 6.0 * self.M * self.N
         if self.kind == "sample":                                 # the logits once, four parameter words and the token per row
             return 2.0 * self.M * self.N + 20.0 * self.M
+        if self.kind == "moe_route":                              # the logits; ids written and read, weights and slot_pos
+            tiles = moe_max_tiles(self.M, self.K, self.N)         # written; the layout's other three arrays written
+            return (2.0 * self.M * self.N + 16.0 * self.M * self.K + 4.0 * MOE_BLOCK_M * tiles + 4.0 * tiles
+                    + 4.0 * (self.N + 1))
+        if self.kind == "moe_gemm":                               # the weights of the experts that can be hit, once; the
+            slots = self.M * self.q                               # T * k useful rows of A and of out
+            return 2.0 * min(self.rows, slots) * self.N * self.K + 2.0 * slots * self.K + 2.0 * slots * self.N
+        if self.kind == "moe_combine":                            # k rows of y per token, out, slot_pos and the weights
+            return 2.0 * self.M * self.K * self.N + 2.0 * self.M * self.N + 8.0 * self.M * self.K
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
@@ -169,6 +218,12 @@ class Op:
             return default_swiglu_workgroups(self.M, self.N)
         if self.kind == "sample":
             return default_sample_workgroups(self.M)
+        if self.kind == "moe_route":
+            return default_moe_route_workgroups(self.M)
+        if self.kind == "moe_gemm":
+            return default_moe_gemm_workgroups(self.M, self.q, self.rows, self.N)
+        if self.kind == "moe_combine":
+            return default_moe_combine_workgroups(self.M, self.N)
         return None
 
 
@@ -374,9 +429,41 @@ LLM_HEAD: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "moe_route", "moe_gemm" and "moe_combine" kinds, which those pinned tables do not list either: the
+# MLP half of a mixture-of-experts decoder block, Qwen3-30B-A3B-like (hidden 2048, 128 experts, top-8, expert width
+# 768) -- residual add + RMSNorm, the router projection (T x 128 x 2048, no ReLU), top-8 routing and the sort into
+# 64-row tiles, the experts' fused gate / up projection (to 2 x 768, A gathered through the permutation), SwiGLU over
+# the P_max rows of the sorted layout, the experts' down projection (to 2048, read in place), the weighted combine
+# back to token order.  1.125 GiB of expert weights.  Each op keeps its own operands, as everywhere in the executor:
+# the routing of the GEMMs' and the combine's operands is computed once on the CPU from random logits.
+#   llm_moe_decode_256    256 tokens: 2,048 slots over 128 experts, 16 rows per expert on average -- every expert's
+#                         weights (1.2 GB) are streamed for a tile that is three quarters padding.  P_max = 10,112 rows
+#                         in 158 tiles, of which the routing uses about 128
+#   llm_moe_prefill_2048  2,048 tokens: 16,384 slots, 128 rows per expert on average; P_max = 24,448 rows in 382 tiles,
+#                         about 320 of them used.  The same weights now meet eight times the rows
+# The three are the eleventh to thirteenth kernel characters; no co-run groups are measured with them yet
+_MOE_D, _MOE_E, _MOE_TOP_K, _MOE_F = 2048, 128, 8, 768
+
+
+def _llm_moe(tokens: int) -> Tuple[Op, ...]:
+    p_max = MOE_BLOCK_M * moe_max_tiles(tokens, _MOE_TOP_K, _MOE_E)
+    return (Op("add_rmsnorm", tokens, _MOE_D), Op("gemm", tokens, _MOE_E, _MOE_D, relu=False),
+            Op("moe_route", tokens, _MOE_E, _MOE_TOP_K),
+            Op("moe_gemm", tokens, 2 * _MOE_F, _MOE_D, rows=_MOE_E, q=_MOE_TOP_K, gather=True),
+            Op("swiglu", p_max, _MOE_F),
+            Op("moe_gemm", tokens, _MOE_D, _MOE_F, rows=_MOE_E, q=_MOE_TOP_K),
+            Op("moe_combine", tokens, _MOE_D, _MOE_TOP_K, rows=_MOE_E))
+
+
+LLM_MOE: Dict[str, Workload] = {
+    "llm_moe_decode_256": Workload("llm_moe_decode_256", "llm_moe_decode", "hip", 256, _llm_moe(256), 1.5),
+    "llm_moe_prefill_2048": Workload("llm_moe_prefill_2048", "llm_moe_prefill", "hip", 2048, _llm_moe(2048), 1.75),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra, staged, long-context, LLM-layer, LLM-block or LLM-head workload by exact name."""
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD):
+    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head or LLM-MoE workload by exact name."""
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE):
         w = table.get(name)
         if w is not None:
             return w
@@ -387,9 +474,9 @@ def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
     the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones, the LLM-block
-    ones, the LLM-head ones last."""
+    ones, the LLM-head ones, the LLM-MoE ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD):
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -533,6 +620,31 @@ def default_sample_workgroups(S: int) -> int:
     return S
 
 
+MOE_ROUTE_TOKENS_PER_WORKGROUP = 4     # one wave per token, 256-thread workgroups (native/hip/moe_route.hip)
+MOE_COMBINE_CHUNKS_PER_WORKGROUP = 256  # one 16-byte output chunk per thread (native/hip/moe_combine.hip)
+
+
+def default_moe_route_workgroups(T: int) -> int:
+    """Workgroups of the routing's top-k launch: one wave per token, ceil(T / 4) (its second launch, the align
+    step, is always ONE workgroup) -- a pure-Python copy of moe_route_workgroups (native/hip/moe_route.hip), pinned
+    against it in tests/test_moe_cpu.py."""
+    return -(-T // MOE_ROUTE_TOKENS_PER_WORKGROUP)
+
+
+def default_moe_gemm_workgroups(T: int, k: int, E: int, N: int) -> int:
+    """Workgroups the grouped expert GEMM launches: moe_max_tiles(T, k, E) row tiles times N / BN column tiles,
+    BN = 128 where N % 128 == 0 and 64 otherwise -- sized for the worst routing; the workgroups of unused tiles
+    exit at once -- a pure-Python copy of moe_gemm_workgroups (native/hip/moe_gemm.hip), pinned like the above."""
+    return moe_max_tiles(T, k, E) * (N // (128 if N % 128 == 0 else 64))
+
+
+def default_moe_combine_workgroups(T: int, D: int) -> int:
+    """Workgroups of the MoE combine: the work flattened over (token, 16-byte chunk of 8 outputs), 256 chunks per
+    workgroup, ceil(T * D / 2048) -- a pure-Python copy of moe_combine_workgroups (native/hip/moe_combine.hip),
+    pinned like the above."""
+    return -(-(T * (D // 8)) // MOE_COMBINE_CHUNKS_PER_WORKGROUP)
+
+
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     """Fraction of the chip's CUs the workload's kernels occupy, weighted by their (roofline)
     time: min(1, workgroups / CUs) per kernel -- GEMM workgroups as the native tile picker
@@ -540,8 +652,9 @@ def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:
     workgroups as default_gather_workgroups and attention workgroups as default_attn_workgroups,
     default_attn_split_workgroups, default_prefill_workgroups and default_rope_append_workgroups count
     them, the norm's one workgroup per row (default_add_rmsnorm_workgroups) and the SwiGLU's one per 8,192
-    outputs (default_swiglu_workgroups), the sampler's one per row of logits (default_sample_workgroups), the
-    stream kernels' grids fill the chip.  A pod that leaves CUs idle alone leaves
+    outputs (default_swiglu_workgroups), the sampler's one per row of logits (default_sample_workgroups), the MoE
+    kernels' as default_moe_route_workgroups, default_moe_gemm_workgroups and default_moe_combine_workgroups count
+    them, the stream kernels' grids fill the chip.  A pod that leaves CUs idle alone leaves
     co-runners room; one that fills the chip alone presses on and suffers from every co-runner
     (models.coldstart)."""
     t = f = 0.0

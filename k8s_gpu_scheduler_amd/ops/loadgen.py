@@ -1,7 +1,7 @@
 """Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
 native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip,
-native/hip/sample.hip).
+native/hip/sample.hip, native/hip/moe_route.hip, native/hip/moe_gemm.hip, native/hip/moe_combine.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
@@ -18,7 +18,11 @@ streams in and two out) and `swiglu(gate_up)` the activation between its fused g
 projections (an element-wise bf16 stream with an exponential and an IEEE division per element);
 `sample_tokens(logits, u, temperature, top_k, top_p)` picks the next token of every sequence from the LM
 head's logits (top-k / top-p sampling: one very long row per sequence, an exact selection, a short sorted
-softmax, a 4-byte result; the caller supplies the uniforms).  Shapes are validated on the host before launch (the kernels
+softmax, a 4-byte result; the caller supplies the uniforms); `moe_route(logits, top_k)`, `moe_gemm(a, w, sorted_ids,
+tile_expert, n_slots, gather_div=)` and `moe_combine(y, slot_pos, topk_w)` are the MLP of a mixture-of-experts block
+-- a top-k softmax and a counting sort of the (token, choice) slots by expert into 64-row tiles, a grouped GEMM with
+one weight matrix per tile (HBM-bound on the weights at decode sizes) and the weighted sum back to token order --
+and `moe_mlp` chains them around `swiglu`.  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
@@ -112,7 +116,41 @@ kernels) rely on:
     kernel trusts the parameters, except that it clamps top_k into [1, 64] itself: check=True verifies
     1 <= top_k <= 64, temperature finite and >= 0 and, on the rows that are not greedy (temperature == 0 or
     top_k == 1), 0 < top_p <= 1 and 0 <= u < 1, on the device first (one sync); check=False never syncs.
-    One workgroup per row (models.workloads.default_sample_workgroups).
+    One workgroup per row (models.workloads.default_sample_workgroups);
+  * the MoE layout (native/hip/moe_route.hip), shared by moe_route, moe_gemm and moe_combine -- the
+    moe_align_block_size scheme of paged-attention servers.  T tokens, E experts, top-k k; n = T * k slots, slot
+    s = t * k + j being token t's j-th choice; moe_max_tiles(T, k, E) = min(n, (n + 63 E) // 64), the least upper
+    bound on sum_e ceil(c_e / 64) over the expert counts c_e; P_max = 64 * moe_max_tiles.  Four int32 arrays:
+      - sorted_ids [P_max]: experts in ascending order; expert e owns the rows [off[e], off[e + 1]) with
+        off[e + 1] - off[e] = 64 * ceil(c_e / 64); its c_e slots come first, in ascending slot order (stable:
+        deterministic, no run-to-run variation); the sentinel n fills the rest of its last tile and every row from
+        off[E] to P_max;
+      - tile_expert [moe_max_tiles]: the expert of each 64-row tile, -1 for the unused trailing tiles;
+      - expert_offsets [E + 1]: off;
+      - slot_pos [n]: the row of sorted_ids that holds slot s (the inverse map).
+    Every element of all four is written by every moe_route launch: they may hold anything before, and a replay
+    gives the same.  moe_align_reference(topk_ids, E) builds them in pure torch on the CPU;
+  * moe_route: logits bf16 [T, E], 2-D with contiguous rows, a row stride >= E and a multiple of 8, the first
+    element 16-byte aligned; E a multiple of 8 in [8, 256], 1 <= top_k <= min(8, E), T * top_k <= 32768.  topk_ids
+    int32 [T, k] and topk_w fp32 [T, k], contiguous; the four layout arrays, 1-D, contiguous, of exactly the sizes
+    above; all six made when None, pairwise disjoint and disjoint from logits.  Two launches: one wave per token
+    (models.workloads.default_moe_route_workgroups), then ONE workgroup for the layout.  T == 0 reads nothing and
+    writes the E + 1 offsets (all 0; moe_max_tiles == 0, so the other arrays are empty);
+  * moe_gemm: a bf16 [R, K] and out bf16 [P_max, N] under the row rules of add_rmsnorm's operands (contiguous rows,
+    a leading dimension >= the row and a multiple of 8, 16-byte aligned); w bf16 [E, N, K] with K-contiguous rows,
+    a row stride >= K and an expert stride that are multiples of 8 (the expert stride is otherwise arbitrary: 0
+    shares one matrix among the experts), 16-byte aligned; N and K positive multiples of 64; sorted_ids int32
+    [P_max] and tile_expert int32 [P_max / 64], contiguous; out disjoint from every input.  Output row i of a used
+    tile is a[src(i)] . w[tile_expert[i // 64]]^T with src(i) = sorted_ids[i] // gather_div for gather_div = k >= 1
+    (the first projection: token rows through the permutation) and src(i) = i for gather_div = 0 (the down
+    projection: the sorted intermediate in place).  The kernel trusts the layout: check=True verifies tile_expert
+    within [-1, E), sorted_ids within [0, n_slots] and every source row of a used tile < R on the device first (one
+    sync); check=False never syncs.  The grid -- P_max / 64 row tiles times N / BN column tiles, BN = 128 where
+    N % 128 == 0, else 64 (models.workloads.default_moe_gemm_workgroups) -- is fixed on the host;
+  * moe_combine: y bf16 [P_max, D] and out bf16 [T, D] under the same row rules, D a positive multiple of 8; topk_w
+    fp32 [T, k] and slot_pos int32 [T * k], contiguous, 1 <= k <= 8; out disjoint from every input.  The kernel
+    trusts slot_pos (moe_route wrote it): every entry names a row of y.  One thread per 16-byte output chunk
+    (models.workloads.default_moe_combine_workgroups).
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -137,7 +175,12 @@ bit-preserved, and the caches are never read.  q_len == 0 and ctx == 0 write not
 launch is idempotent.  add_rmsnorm reads the T x D windows of x and residual and the D elements of
 weight and writes the T x D windows of out and residual_out; swiglu reads the T x 2F window of gate_up and
 writes the T x F window of out.  sample_tokens reads the S x V window of logits and the S elements of u,
-temperature, top_k and top_p and writes the S elements of out.  The padding between the rows of a strided
+temperature, top_k and top_p and writes the S elements of out.  moe_route reads the T x E window of logits and writes
+every element of its six outputs.  moe_gemm reads sorted_ids and tile_expert, the K elements of the rows of a that the
+valid rows of used tiles name -- never a pad row's own, and nothing for an unused tile -- and the N x K windows of the
+experts that own a used tile; it writes the N columns of every row of a used tile (a pad row, sorted_ids[i] >= n_slots,
+as +0.0, 0x0000) and leaves the rows of unused tiles bit-preserved.  moe_combine reads slot_pos, topk_w and the D
+elements of the T * k rows of y that slot_pos names and writes the T x D window of out.  The padding between the rows of a strided
 operand is neither read nor written.
 
 Numeric contract (pinned bitwise by tests/test_gpu_numeric_edges.py against an integer definition
@@ -260,6 +303,22 @@ of the conversion and float64 sums):
     Memory:
       - Nothing outside the S x V window and the five [S] vectors is read.
       - Only out[0..S) is written.
+  * moe_route (pinned by tests/test_gpu_moe_route_exact.py).  Selection: the k largest logits of a token ranked by
+    (value descending, index ascending); comparisons are on values (+0.0 == -0.0) and ties go to the lowest index, so
+    topk_ids is exact for any finite or +-Inf input.  Weights, in fp32: e_j = exp2((l_j - l_0) * 1.44269504f) -- one
+    subtraction, one multiply, the hardware v_exp_f32 --, their sum over j = 0 .. k - 1 in that order, and
+    topk_w[t, j] = e_j / sum, an IEEE division: softmax-then-renormalise over the k selected logits.  Equal logits
+    give exactly 1 / k for k a power of two; k = 1 gives exactly 1.0.  A row that holds a NaN, or whose maximum is
+    -Inf, has unspecified weights; its ids are still k distinct values in [0, E), and nothing downstream can index
+    out of range because of data.  The layout has no float in it, integer atomics only count, and the order inside
+    an expert is the stable one: two launches are bit-identical;
+  * moe_gemm (pinned by tests/test_gpu_moe_gemm_exact.py): no bias, no activation; out = bf16(acc), one rounding to
+    nearest even of an fp32 MFMA accumulation (v_mfma_f32_16x16x32_bf16) whose K order is fixed -- no split-K, no
+    atomics, so launches repeat bit for bit -- and the same for every row of a tile: a row's result does not depend
+    on where in a tile it sits.  The NaN rule is the GEMMs';
+  * moe_combine (pinned by tests/test_gpu_moe_combine_exact.py): acc = 0.0f, then for j = 0 .. k - 1 in that order
+    acc = fmaf(topk_w[t, j], fp32(y[slot_pos[t k + j], c]), acc), fused whatever the contraction setting, and one
+    rounding to bf16.  Nothing is skipped (0 * NaN is NaN): a NaN reaches its own (t, column) and no other.
 """
 from __future__ import annotations
 
@@ -271,6 +330,8 @@ from .. import _native
 from ..models.workloads import ATTN_BLOCK_TOKENS, ATTN_HEAD_DIM          # the decode-attention kernel's fixed sizes
 from ..models.workloads import (ATTN_MAX_KV_SPLITS, decode_split_range,      # the split-KV decode's rules, pure Python
                                 decode_split_workspace_floats)
+from ..models.workloads import (MOE_BLOCK_M, MOE_MAX_EXPERTS, MOE_MAX_SLOTS, MOE_MAX_TOP_K,      # the MoE layout's sizes
+                                moe_max_tiles)
 
 BM, BN, BK = 64, 64, 64          # minimum granularity; the tile (128x128 / 64x128 / 64x64) is picked per shape
 
@@ -1001,6 +1062,288 @@ def sample_tokens(logits: torch.Tensor, u: torch.Tensor, temperature: torch.Tens
         h.sample_topk_bf16(logits.data_ptr(), u.data_ptr(), temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(),
                            out.data_ptr(), S, V, ld, sp)
     return out
+
+
+def moe_topk_reference(logits: torch.Tensor, top_k: int):
+    """(topk_ids int32 [T, k], topk_w fp32 [T, k]) of moe_route in pure torch, on logits' device: the k largest by
+    (value descending, index ascending) -- a stable descending sort of the values, so ties and +-0 go to the lowest
+    index -- and the softmax over the selected logits, computed in float64 and cast once.  The ids are the kernel's
+    exactly for rows without a NaN; the weights are the kernel's within its fp32 rounding."""
+    order = logits.double().sort(dim=1, descending=True, stable=True)
+    ids, l = order.indices[:, :top_k], order.values[:, :top_k]
+    e = torch.exp2((l - l[:, :1]) * 1.4426950408889634)
+    return ids.to(torch.int32), (e / e.sum(dim=1, keepdim=True)).to(torch.float32)
+
+
+def moe_align_reference(topk_ids: torch.Tensor, E: int):
+    """(sorted_ids, tile_expert, expert_offsets, slot_pos) of the MoE layout for topk_ids int [T, k] with entries
+    in [0, E), in pure torch on the CPU (int32): the oracle of the GPU tests and what the executor's operand
+    builders route with."""
+    if topk_ids.dim() != 2:
+        raise ValueError(f"moe_align_reference: topk_ids must be [T, k] (got {tuple(topk_ids.shape)})")
+    T, k = topk_ids.shape
+    ids = topk_ids.reshape(-1).to("cpu", torch.int64)
+    n = T * k
+    if n and not (0 <= int(ids.min()) and int(ids.max()) < E):
+        raise ValueError(f"moe_align_reference: an expert id is outside [0, {E})")
+    tiles = moe_max_tiles(T, k, E)
+    counts = torch.bincount(ids, minlength=E)
+    padded = (counts + MOE_BLOCK_M - 1) // MOE_BLOCK_M * MOE_BLOCK_M
+    off = torch.zeros(E + 1, dtype=torch.int64)
+    off[1:] = padded.cumsum(0)
+    order = ids.sort(stable=True).indices                             # the slots by (expert, slot)
+    first = counts.cumsum(0) - counts                                 # of each expert, in that order
+    e_of = ids[order]
+    pos = off[e_of] + torch.arange(n) - first[e_of]
+    sorted_ids = torch.full((tiles * MOE_BLOCK_M,), n, dtype=torch.int64)
+    sorted_ids[pos] = order
+    slot_pos = torch.empty(n, dtype=torch.int64)
+    slot_pos[order] = pos
+    tile_expert = torch.full((tiles,), -1, dtype=torch.int64)
+    tile_expert[:int(off[E]) // MOE_BLOCK_M] = torch.repeat_interleave(torch.arange(E), padded // MOE_BLOCK_M)
+    return tuple(t.to(torch.int32) for t in (sorted_ids, tile_expert, off, slot_pos))
+
+
+def _moe_vector(name: str, nm: str, t: Optional[torch.Tensor], shape: tuple, dtype: torch.dtype, device) -> torch.Tensor:
+    """An int32 / fp32 operand of the MoE ops: made when None, else of exactly this dtype and shape, contiguous."""
+    what = "int32" if dtype == torch.int32 else "fp32"
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if t.dtype != dtype:
+        raise TypeError(f"{name} expects an {what} {nm} (got {t.dtype})")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: {nm} must be contiguous of shape {tuple(shape)} (got {tuple(t.shape)})")
+    return t
+
+
+def _moe_route_sizes(name: str, T: int, E: int, top_k) -> None:
+    if E < 8 or E > MOE_MAX_EXPERTS or E % 8:
+        raise ValueError(f"{name}: E = {E} must be a multiple of 8 in [8, {MOE_MAX_EXPERTS}]")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= min(MOE_MAX_TOP_K, E):
+        raise ValueError(f"{name}: top_k = {top_k!r} must be an int in [1, min({MOE_MAX_TOP_K}, E)]")
+    if T * top_k > MOE_MAX_SLOTS:
+        raise ValueError(f"{name}: T * top_k = {T * top_k} is more than {MOE_MAX_SLOTS} slots")
+
+
+def moe_route(logits: torch.Tensor, top_k: int, *, topk_ids: Optional[torch.Tensor] = None,
+              topk_w: Optional[torch.Tensor] = None, sorted_ids: Optional[torch.Tensor] = None,
+              tile_expert: Optional[torch.Tensor] = None, expert_offsets: Optional[torch.Tensor] = None,
+              slot_pos: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None, check: bool = True):
+    """MoE routing of T tokens over E experts from the router's logits bf16 [T, E] (E a multiple of 8 in [8, 256],
+    1 <= top_k <= min(8, E), T * top_k <= 32768); returns (topk_ids, topk_w, sorted_ids, tile_expert, expert_offsets,
+    slot_pos), each made when None.  topk_ids int32 [T, k]: the k largest logits by (value descending, index
+    ascending); topk_w fp32 [T, k] = e_j / sum e with e_j = exp2((l_j - l_0) * 1.44269504f) in fp32 (softmax, then
+    renormalised over the k).  The other four are the sorted, tile-aligned layout of the n = T * k slots
+    (s = t * k + j) that moe_gemm and moe_combine take: sorted_ids int32 [64 * moe_max_tiles(T, k, E)] -- expert e
+    owns rows [off[e], off[e + 1]), a multiple of 64, its slots first in ascending order, n elsewhere --, tile_expert
+    int32 [moe_max_tiles] (-1: unused), expert_offsets int32 [E + 1] (off) and slot_pos int32 [n] (the inverse map).
+    Every element of the six is written.  Nothing here depends on data, so there is nothing to check on the device:
+    `check` is accepted for symmetry with the other ops and neither value ever syncs.  T == 0 reads nothing and
+    writes the E + 1 zero offsets."""
+    name = "moe_route"
+    outs = (("topk_ids", topk_ids), ("topk_w", topk_w), ("sorted_ids", sorted_ids), ("tile_expert", tile_expert),
+            ("expert_offsets", expert_offsets), ("slot_pos", slot_pos))
+    _check_devices(name, logits, *(t for _, t in outs))
+    if logits.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 logits (got {logits.dtype})")
+    if logits.dim() == 2:                                            # the E rule before the stride rules it implies
+        _moe_route_sizes(name, logits.shape[0], logits.shape[1], top_k)
+    ld = _bf16_rows(name, "logits", logits)
+    T, E = logits.shape
+    k, n, tiles, dev = top_k, T * top_k, moe_max_tiles(T, top_k, E), logits.device
+    topk_ids = _moe_vector(name, "topk_ids", topk_ids, (T, k), torch.int32, dev)
+    topk_w = _moe_vector(name, "topk_w", topk_w, (T, k), torch.float32, dev)
+    sorted_ids = _moe_vector(name, "sorted_ids", sorted_ids, (tiles * MOE_BLOCK_M,), torch.int32, dev)
+    tile_expert = _moe_vector(name, "tile_expert", tile_expert, (tiles,), torch.int32, dev)
+    expert_offsets = _moe_vector(name, "expert_offsets", expert_offsets, (E + 1,), torch.int32, dev)
+    slot_pos = _moe_vector(name, "slot_pos", slot_pos, (n,), torch.int32, dev)
+    result = (topk_ids, topk_w, sorted_ids, tile_expert, expert_offsets, slot_pos)
+    named = list(zip((nm for nm, _ in outs), result))
+    for i, (nm, t) in enumerate(named):
+        if _overlap(t, logits):
+            raise ValueError(f"{name}: {nm} overlaps logits")
+        for other, u in named[:i]:
+            if _overlap(t, u):
+                raise ValueError(f"{name}: {nm} overlaps {other}")
+    h = _native.hip()
+    with torch.cuda.device(dev):
+        h.moe_route_bf16(logits.data_ptr(), topk_ids.data_ptr(), topk_w.data_ptr(), sorted_ids.data_ptr(),
+                         tile_expert.data_ptr(), expert_offsets.data_ptr(), slot_pos.data_ptr(), T, E, k, ld,
+                         _stream_ptr(stream, dev))
+    return result
+
+
+def moe_gemm(a: torch.Tensor, w: torch.Tensor, sorted_ids: torch.Tensor, tile_expert: torch.Tensor, n_slots: int, *,
+             gather_div: int, out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+             check: bool = True) -> torch.Tensor:
+    """The grouped expert GEMM of an MoE MLP over the sorted layout of moe_route: for every row i of a used tile,
+    out[i, :] = bf16(a[src(i), :] . w[tile_expert[i // 64]]^T) -- a bf16 [R, K], w bf16 [E, N, K], out bf16
+    [P_max, N] (made when None), N and K multiples of 64, fp32 accumulation, no bias, no activation.
+    gather_div = k >= 1: src(i) = sorted_ids[i] // k, the first projection reading token rows through the
+    permutation; gather_div = 0: src(i) = i, the down projection reading the sorted intermediate in place.  A pad
+    row (sorted_ids[i] >= n_slots) reads nothing of its own and is written as +0.0; the rows of unused tiles
+    (tile_expert == -1) are neither read nor written -- a fresh `out` keeps whatever torch.empty gave them.
+    check=True verifies on the device first (one sync): tile_expert within [-1, E), sorted_ids within [0, n_slots]
+    and every source row of a used tile < R.  check=False never syncs: for callers that took the layout from
+    moe_route, and under graph capture.  No used tile (or P_max == 0) writes nothing."""
+    name = "moe_gemm"
+    _check_devices(name, a, w, sorted_ids, tile_expert, out)
+    if w.dtype != torch.bfloat16:
+        raise TypeError(f"{name} expects bf16 tensors (w is {w.dtype})")
+    if sorted_ids.dtype != torch.int32 or tile_expert.dtype != torch.int32:
+        raise TypeError(f"{name} expects an int32 sorted_ids and tile_expert")
+    lda = _bf16_rows(name, "a", a)
+    R, K = a.shape
+    if w.dim() != 3 or w.shape[2] != K:
+        raise ValueError(f"{name}: w must be [E, N, K = {K}] (got {tuple(w.shape)})")
+    E, N, _ = w.shape
+    if E < 1 or E > MOE_MAX_EXPERTS:
+        raise ValueError(f"{name}: E = {E} must be in [1, {MOE_MAX_EXPERTS}]")
+    if N <= 0 or K <= 0 or N % 64 or K % 64:
+        raise ValueError(f"{name}: N = {N} and K = {K} must be positive multiples of 64")
+    if w.stride(2) != 1:
+        raise ValueError(f"{name}: w must have K-contiguous rows")
+    ldw, se = w.stride(1), (w.stride(0) if E > 1 else 0)
+    if ldw < K or ldw % 8 or ldw >= 2 ** 31:
+        raise ValueError(f"{name}: w row stride {ldw} must be >= {K}, a multiple of 8 and below 2^31")
+    if se < 0 or se % 8:
+        raise ValueError(f"{name}: w expert stride {se} must be a non-negative multiple of 8")
+    if w.data_ptr() % 16:
+        raise ValueError(f"{name}: w must be 16-byte aligned")
+    if sorted_ids.dim() != 1 or tile_expert.dim() != 1 or not sorted_ids.is_contiguous() or not tile_expert.is_contiguous():
+        raise ValueError(f"{name}: sorted_ids and tile_expert must be contiguous vectors")
+    tiles = tile_expert.numel()
+    if sorted_ids.numel() != tiles * MOE_BLOCK_M:
+        raise ValueError(f"{name}: sorted_ids has {sorted_ids.numel()} rows, the {tiles} tiles of tile_expert need "
+                         f"{tiles * MOE_BLOCK_M}")
+    if isinstance(n_slots, bool) or not isinstance(n_slots, int) or not 0 <= n_slots <= MOE_MAX_SLOTS:
+        raise ValueError(f"{name}: n_slots = {n_slots!r} must be an int in [0, {MOE_MAX_SLOTS}]")
+    if isinstance(gather_div, bool) or not isinstance(gather_div, int) or not 0 <= gather_div <= MOE_MAX_TOP_K:
+        raise ValueError(f"{name}: gather_div = {gather_div!r} must be 0 or the top-k, an int in [1, {MOE_MAX_TOP_K}]")
+    P = tiles * MOE_BLOCK_M
+    if out is None:
+        out = torch.empty((P, N), dtype=torch.bfloat16, device=a.device)
+    ldc = _bf16_rows(name, "out", out, N)
+    if out.shape[0] != P:
+        raise ValueError(f"{name}: out has {out.shape[0]} rows, the layout {P}")
+    for nm, t in (("a", a), ("w", w), ("sorted_ids", sorted_ids), ("tile_expert", tile_expert)):
+        if _overlap(out, t):
+            raise ValueError(f"{name}: out overlaps {nm}")
+    if tiles == 0:
+        return out
+    h = _native.hip()
+    with torch.cuda.device(a.device):
+        sp = _stream_ptr(stream, a.device)
+        if check:
+            with _launch_stream(stream, a.device):
+                used = (tile_expert >= 0).repeat_interleave(MOE_BLOCK_M)
+                valid = used & (sorted_ids >= 0) & (sorted_ids < n_slots)
+                src = sorted_ids // gather_div if gather_div else torch.arange(P, dtype=torch.int32, device=a.device)
+                bad = torch.stack([((tile_expert < -1) | (tile_expert >= E)).any(),
+                                   ((sorted_ids < 0) | (sorted_ids > n_slots)).any(),
+                                   (valid & (src >= R)).any()]).tolist()                      # the one sync
+            if bad[0]:
+                raise ValueError(f"{name}: a tile_expert entry is outside [-1, {E})")
+            if bad[1]:
+                raise ValueError(f"{name}: a sorted_ids entry is outside [0, {n_slots}]")
+            if bad[2]:
+                raise ValueError(f"{name}: a source row is past the {R} rows of a")
+        h.moe_gemm_bf16(a.data_ptr(), w.data_ptr(), sorted_ids.data_ptr(), tile_expert.data_ptr(), out.data_ptr(), tiles,
+                        n_slots, gather_div, N, K, lda, ldw, se, ldc, sp)
+    return out
+
+
+def moe_combine(y: torch.Tensor, slot_pos: torch.Tensor, topk_w: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+                stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The weighted sum of each token's k expert outputs back in token order: out[t, :] = bf16(sum over
+    j = 0 .. k - 1 of topk_w[t, j] * y[slot_pos[t * k + j], :]) -- y bf16 [P_max, D] in the sorted layout of moe_route,
+    slot_pos int32 [T * k], topk_w fp32 [T, k] (1 <= k <= 8), out bf16 [T, D] (made when None), D a multiple of 8.
+    In fp32, acc = 0.0f and acc = fmaf(w, y, acc) for j = 0 .. k - 1 in that order, then one rounding; nothing is
+    skipped, so a NaN reaches exactly its own (t, column).  slot_pos is trusted (moe_route wrote it): every entry
+    names a row of y.  T == 0 launches nothing; replaying a launch gives the same."""
+    name = "moe_combine"
+    _check_devices(name, y, slot_pos, topk_w, out)
+    if topk_w.dtype != torch.float32:
+        raise TypeError(f"{name} expects an fp32 topk_w (got {topk_w.dtype})")
+    if slot_pos.dtype != torch.int32:
+        raise TypeError(f"{name} expects an int32 slot_pos (got {slot_pos.dtype})")
+    if y.dim() == 2 and y.dtype == torch.bfloat16 and (y.shape[1] <= 0 or y.shape[1] % 8):
+        raise ValueError(f"{name}: D = {y.shape[1]} must be a positive multiple of 8")
+    ld_y = _bf16_rows(name, "y", y)
+    D = y.shape[1]
+    if topk_w.dim() != 2 or not 1 <= topk_w.shape[1] <= MOE_MAX_TOP_K or not topk_w.is_contiguous():
+        raise ValueError(f"{name}: topk_w must be contiguous [T, k] with 1 <= k <= {MOE_MAX_TOP_K} (got {tuple(topk_w.shape)})")
+    T, k = topk_w.shape
+    if slot_pos.dim() != 1 or slot_pos.numel() != T * k or not slot_pos.is_contiguous():
+        raise ValueError(f"{name}: slot_pos must be a contiguous vector of length T * k = {T * k} (got {tuple(slot_pos.shape)})")
+    if out is None:
+        out = torch.empty((T, D), dtype=torch.bfloat16, device=y.device)
+    ld_out = _bf16_rows(name, "out", out, D)
+    if out.shape[0] != T:
+        raise ValueError(f"{name}: out {tuple(out.shape)} does not match the {T} tokens of topk_w")
+    for nm, t in (("y", y), ("slot_pos", slot_pos), ("topk_w", topk_w)):
+        if _overlap(out, t):
+            raise ValueError(f"{name}: out overlaps {nm}")
+    if T == 0:
+        return out
+    h = _native.hip()
+    with torch.cuda.device(y.device):
+        h.moe_combine_bf16(y.data_ptr(), slot_pos.data_ptr(), topk_w.data_ptr(), out.data_ptr(), T, D, k, ld_y, ld_out,
+                           _stream_ptr(stream, y.device))
+    return out
+
+
+def moe_workspace(T: int, E: int, top_k: int, D: int, F: int, device) -> dict:
+    """The intermediates of moe_mlp for T tokens, E experts, top-k, hidden size D and expert width F, allocated once
+    (a caller under graph capture passes them in: they must outlive the graph): the six outputs of moe_route, h13
+    bf16 [P_max, 2F], act bf16 [P_max, F] and y bf16 [P_max, D].  h13 starts as zeros: the rows of unused tiles are
+    never written by moe_gemm but are read by swiglu, whose output nothing then reads -- zeros keep that dead work
+    finite."""
+    _moe_route_sizes("moe_workspace", T, E, top_k)
+    tiles = moe_max_tiles(T, top_k, E)
+    P = tiles * MOE_BLOCK_M
+    i32 = dict(dtype=torch.int32, device=device)
+    bf = dict(dtype=torch.bfloat16, device=device)
+    return {"topk_ids": torch.empty((T, top_k), **i32), "topk_w": torch.empty((T, top_k), dtype=torch.float32, device=device),
+            "sorted_ids": torch.empty(P, **i32), "tile_expert": torch.empty(tiles, **i32),
+            "expert_offsets": torch.empty(E + 1, **i32), "slot_pos": torch.empty(T * top_k, **i32),
+            "h13": torch.zeros((P, 2 * F), **bf), "act": torch.empty((P, F), **bf), "y": torch.empty((P, D), **bf)}
+
+
+def moe_mlp(x: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, top_k: int, *,
+            workspace: Optional[dict] = None, out: Optional[torch.Tensor] = None,
+            stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The MLP of a mixture-of-experts block: x bf16 [T, D], router_logits bf16 [T, E], w13 bf16 [E, 2F, D] (each
+    expert's fused gate / up projection), w2 bf16 [E, D, F] (its down projection); returns out bf16 [T, D].  Five
+    ops on one stream -- moe_route, moe_gemm gathered (gather_div = top_k) to h13 [P_max, 2F], swiglu to act
+    [P_max, F], moe_gemm in place (gather_div = 0) to y [P_max, D], moe_combine -- with check=False throughout: it
+    never syncs and can be captured in a graph.  workspace: moe_workspace(T, E, top_k, D, F, device), made on the
+    launch stream when None.  The result is bit for bit that of the five calls made one by one."""
+    name = "moe_mlp"
+    dev = _check_devices(name, x, router_logits, w13, w2, out)
+    for nm, t in (("x", x), ("router_logits", router_logits), ("w13", w13), ("w2", w2)):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"{name} expects bf16 tensors ({nm} is {t.dtype})")
+    if x.dim() != 2 or router_logits.dim() != 2 or w13.dim() != 3 or w2.dim() != 3:
+        raise ValueError(f"{name} expects x [T, D], router_logits [T, E], w13 [E, 2F, D] and w2 [E, D, F]")
+    (T, D), E, F = x.shape, router_logits.shape[1], w2.shape[2]
+    if router_logits.shape[0] != T or tuple(w13.shape) != (E, 2 * F, D) or tuple(w2.shape) != (E, D, F):
+        raise ValueError(f"{name}: x {tuple(x.shape)}, router_logits {tuple(router_logits.shape)}, w13 {tuple(w13.shape)} "
+                         f"and w2 {tuple(w2.shape)} disagree on T, D, E or F")
+    _moe_route_sizes(name, T, E, top_k)
+    if workspace is None:
+        with _launch_stream(stream, dev):
+            workspace = moe_workspace(T, E, top_k, D, F, dev)
+    ws = workspace
+    _, topk_w, sorted_ids, tile_expert, _, slot_pos = moe_route(
+        router_logits, top_k, topk_ids=ws["topk_ids"], topk_w=ws["topk_w"], sorted_ids=ws["sorted_ids"],
+        tile_expert=ws["tile_expert"], expert_offsets=ws["expert_offsets"], slot_pos=ws["slot_pos"], stream=stream,
+        check=False)
+    n = T * top_k
+    moe_gemm(x, w13, sorted_ids, tile_expert, n, gather_div=top_k, out=ws["h13"], stream=stream, check=False)
+    swiglu(ws["h13"], out=ws["act"], stream=stream)
+    moe_gemm(ws["act"], w2, sorted_ids, tile_expert, n, gather_div=0, out=ws["y"], stream=stream, check=False)
+    return moe_combine(ws["y"], slot_pos, topk_w, out=out, stream=stream)
 
 
 def gemm_flops(M: int, N: int, K: int) -> float:

@@ -6,6 +6,7 @@
     python -m k8s_gpu_scheduler_amd.ops.podrun --workload llm_decode_long_8 --iters 2
     python -m k8s_gpu_scheduler_amd.ops.podrun --workload llm_block_decode_256 --iters 2
     python -m k8s_gpu_scheduler_amd.ops.podrun --workload llm_head_decode_256 --iters 2
+    python -m k8s_gpu_scheduler_amd.ops.podrun --workload llm_moe_decode_256 --iters 2
 
 The device comes from the container env the scheduler wrote (ROCR_VISIBLE_DEVICES /
 HIP_VISIBLE_DEVICES, and HSA_CU_MASK for a Guaranteed share -- the ROCm runtime applies

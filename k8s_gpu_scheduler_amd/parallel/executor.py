@@ -181,6 +181,50 @@ def _sample_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return torch.empty(o.M, dtype=torch.int32, device=device), logits, u, temperature, top_k, top_p
 
 
+MOE_PATTERN_EXPERTS = 4           # experts of the CPU-generated pattern the expert weights repeat
+
+
+def _moe_routing(T: int, E: int, k: int, g: torch.Generator) -> tuple:
+    """(topk_w, sorted_ids, tile_expert, slot_pos) on the CPU for T tokens with randn router logits: the routing of
+    a moe_gemm / moe_combine op's operands, computed once with loadgen's pure-torch references."""
+    logits = torch.randn(T, E, generator=g).to(torch.bfloat16)
+    ids, w = loadgen.moe_topk_reference(logits, k)
+    sorted_ids, tile_expert, _, slot_pos = loadgen.moe_align_reference(ids, E)
+    return w, sorted_ids, tile_expert, slot_pos
+
+
+def _moe_route_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(topk_ids, logits, topk_w, sorted_ids, tile_expert, expert_offsets, slot_pos): M tokens' randn logits over N
+    experts in bf16, and the six outputs of the top-K routing."""
+    logits = torch.randn(o.M, o.N, generator=g).to(torch.bfloat16).to(device)
+    tiles = loadgen.moe_max_tiles(o.M, o.K, o.N)
+    i32 = dict(dtype=torch.int32, device=device)
+    return (torch.empty(o.M, o.K, **i32), logits, torch.empty(o.M, o.K, dtype=torch.float32, device=device),
+            torch.empty(tiles * loadgen.MOE_BLOCK_M, **i32), torch.empty(tiles, **i32), torch.empty(o.N + 1, **i32),
+            torch.empty(o.M * o.K, **i32))
+
+
+def _moe_gemm_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, a, w, sorted_ids, tile_expert): the routing of M tokens over o.rows experts (top-o.q) from random logits;
+    a is randn -- the [M, K] token rows with o.gather, else the [P_max, K] sorted intermediate --; the weights
+    [o.rows, N, K] repeat a pattern of four experts of uniform values in +-0.05.  out starts as zeros: the rows of
+    the tiles the routing leaves unused are never written."""
+    _, sorted_ids, tile_expert, _ = _moe_routing(o.M, o.rows, o.q, g)
+    P = sorted_ids.numel()
+    a = torch.randn(o.M if o.gather else P, o.K, generator=g).to(torch.bfloat16).to(device)
+    pat = ((torch.rand(min(o.rows, MOE_PATTERN_EXPERTS), o.N, o.K, generator=g) * 2 - 1) * 0.05).to(torch.bfloat16).to(device)
+    out = torch.zeros(P, o.N, dtype=torch.bfloat16, device=device)
+    return out, a, _repeat(pat, o.rows), sorted_ids.to(device), tile_expert.to(device)
+
+
+def _moe_combine_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, y, slot_pos, topk_w): the routing of M tokens over o.rows experts (top-K) from random logits, y randn
+    [P_max, N] in bf16."""
+    w, sorted_ids, _, slot_pos = _moe_routing(o.M, o.rows, o.K, g)
+    y = torch.randn(sorted_ids.numel(), o.N, generator=g).to(torch.bfloat16).to(device)
+    return torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device), y, slot_pos.to(device), w.to(device)
+
+
 def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return tuple(torch.ones(o.n_floats, dtype=torch.float32, device=device) for _ in range(3))
 
@@ -188,7 +232,7 @@ def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
 # The launches look their loadgen entry point up when called (tests replace the attributes).  The
 # gather's indices, and the attention's ctx_lens and block ids, are in range by construction: no
 # check, no sync (this runs under graph capture); so are the prefill's q_start and max_q_len, and the
-# sampler's parameters.
+# sampler's parameters, and the MoE ops' layouts (the CPU reference built them).
 def _launch_gemm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     a, bt, bias, c = t
     loadgen.gemm(a, bt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
@@ -240,6 +284,23 @@ def _launch_sample(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.sample_tokens(logits, u, temperature, top_k, top_p, out=out, stream=st, check=False)
 
 
+def _launch_moe_route(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    topk_ids, logits, topk_w, sorted_ids, tile_expert, expert_offsets, slot_pos = t
+    loadgen.moe_route(logits, o.K, topk_ids=topk_ids, topk_w=topk_w, sorted_ids=sorted_ids, tile_expert=tile_expert,
+                      expert_offsets=expert_offsets, slot_pos=slot_pos, stream=st, check=False)
+
+
+def _launch_moe_gemm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, a, w, sorted_ids, tile_expert = t
+    loadgen.moe_gemm(a, w, sorted_ids, tile_expert, o.M * o.q, gather_div=o.q if o.gather else 0, out=out, stream=st,
+                     check=False)
+
+
+def _launch_moe_combine(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, y, slot_pos, topk_w = t
+    loadgen.moe_combine(y, slot_pos, topk_w, out=out, stream=st)
+
+
 def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     x, y, z = t
     loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
@@ -251,7 +312,9 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # table, idx, offsets); attn (out, q, k_cache, v_cache, table, ctx); prefill the same and q_start;
 # attn_split the same and the workspace; rope_append (q_out, qkv, cos_sin, k_cache, v_cache, table, ctx,
 # q_start); add_rmsnorm (y, res_out, x, residual, weight); swiglu (out, gate_up); sample (out, logits, u,
-# temperature, top_k, top_p); triad (x, y, z), x = y + s z.
+# temperature, top_k, top_p); moe_route (topk_ids, logits, topk_w, sorted_ids, tile_expert, expert_offsets,
+# slot_pos); moe_gemm (out, a, w, sorted_ids, tile_expert); moe_combine (out, y, slot_pos, topk_w); triad (x, y, z),
+# x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -263,6 +326,9 @@ OP_KINDS = {
     "add_rmsnorm": (_add_rmsnorm_operands, _launch_add_rmsnorm, 0),
     "swiglu": (_swiglu_operands, _launch_swiglu, 0),
     "sample": (_sample_operands, _launch_sample, 0),
+    "moe_route": (_moe_route_operands, _launch_moe_route, 0),
+    "moe_gemm": (_moe_gemm_operands, _launch_moe_gemm, 0),
+    "moe_combine": (_moe_combine_operands, _launch_moe_combine, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -100,6 +100,35 @@ void sample_topk_bf16(uintptr_t logits, uintptr_t u, uintptr_t temperature, uint
                       uintptr_t out, int S, int V, int64_t ld_logits, uintptr_t stream);
 // workgroups of that launch: one per row
 int sample_workgroups(int S);
+// Mixture-of-experts MLP -- native/hip/moe_route.hip, moe_gemm.hip, moe_combine.hip.  They share one layout of the
+// n = T * k (token, choice) slots, s = t * k + j: sorted_ids int32 [64 * moe_max_tiles] (expert e owns rows
+// [off[e], off[e + 1]), a multiple of 64; its slots first, ascending; n elsewhere), tile_expert int32 [moe_max_tiles]
+// (-1: unused), expert_offsets int32 [E + 1] (off), slot_pos int32 [n] (the row that holds slot s).
+// the least upper bound on the used 64-row tiles: min(T k, (T k + 63 E) / 64); T k <= 32768, k <= 8, E <= 256
+int moe_max_tiles(int T, int k, int E);
+// Routing: logits bf16 [T, E] (row stride ld_logits; E a multiple of 8 in [8, 256], k <= min(8, E)).  Launch 1: the k
+// largest logits per token by (value descending, index ascending) to topk_ids int32 [T, k], and topk_w fp32 [T, k] =
+// e_j / sum e with e_j = exp2((l_j - l_0) * 1.44269504f).  Launch 2 (one workgroup): the four layout arrays, every
+// element written.  T == 0 reads nothing and writes the E + 1 offsets
+void moe_route_bf16(uintptr_t logits, uintptr_t topk_ids, uintptr_t topk_w, uintptr_t sorted_ids, uintptr_t tile_expert,
+                    uintptr_t expert_offsets, uintptr_t slot_pos, int T, int E, int k, int64_t ld_logits,
+                    uintptr_t stream);
+// workgroups of the top-k launch: one wave per token, ceil(T / 4) (the align launch is one workgroup)
+int moe_route_workgroups(int T);
+// Grouped expert GEMM: out[i, :] = bf16(a[src(i), :] . w[tile_expert[i / 64]]^T) for the rows of used tiles; w bf16
+// [E, N, K] (row stride ldw, expert stride expert_stride), N and K multiples of 64; src(i) = sorted_ids[i] / gather_div,
+// or i with gather_div == 0; a pad row (sorted_ids[i] >= n_slots) is written as +0.0, unused tiles are not touched
+void moe_gemm_bf16(uintptr_t a, uintptr_t w, uintptr_t sorted_ids, uintptr_t tile_expert, uintptr_t out, int max_tiles,
+                   int n_slots, int gather_div, int N, int K, int64_t lda, int64_t ldw, int64_t expert_stride,
+                   int64_t ldc, uintptr_t stream);
+// workgroups of that launch: moe_max_tiles(T, k, E) * (N / BN), BN = 128 where N % 128 == 0, else 64
+int moe_gemm_workgroups(int T, int k, int E, int N);
+// Combine: out[t, :] = bf16(sum_j topk_w[t, j] * y[slot_pos[t k + j], :]), fma in the order j = 0 .. k - 1; y bf16
+// [P_max, D], out bf16 [T, D], D a multiple of 8
+void moe_combine_bf16(uintptr_t y, uintptr_t slot_pos, uintptr_t topk_w, uintptr_t out, int T, int D, int k, int64_t ld_y,
+                      int64_t ld_out, uintptr_t stream);
+// workgroups of that launch: one thread per 16-byte output chunk, ceil(T * D / 2048)
+int moe_combine_workgroups(int T, int D);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

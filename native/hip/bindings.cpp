@@ -104,6 +104,20 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("top_k"), py::arg("top_p"), py::arg("out"), py::arg("S"), py::arg("V"), py::arg("ld_logits"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
   m.def("sample_workgroups", &gs::sample_workgroups, py::arg("S"));
+  m.def("moe_max_tiles", &gs::moe_max_tiles, py::arg("T"), py::arg("k"), py::arg("E"));
+  m.def("moe_route_bf16", &gs::moe_route_bf16, py::arg("logits"), py::arg("topk_ids"), py::arg("topk_w"),
+        py::arg("sorted_ids"), py::arg("tile_expert"), py::arg("expert_offsets"), py::arg("slot_pos"), py::arg("T"),
+        py::arg("E"), py::arg("k"), py::arg("ld_logits"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("moe_route_workgroups", &gs::moe_route_workgroups, py::arg("T"));
+  m.def("moe_gemm_bf16", &gs::moe_gemm_bf16, py::arg("a"), py::arg("w"), py::arg("sorted_ids"), py::arg("tile_expert"),
+        py::arg("out"), py::arg("max_tiles"), py::arg("n_slots"), py::arg("gather_div"), py::arg("N"), py::arg("K"),
+        py::arg("lda"), py::arg("ldw"), py::arg("expert_stride"), py::arg("ldc"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("moe_gemm_workgroups", &gs::moe_gemm_workgroups, py::arg("T"), py::arg("k"), py::arg("E"), py::arg("N"));
+  m.def("moe_combine_bf16", &gs::moe_combine_bf16, py::arg("y"), py::arg("slot_pos"), py::arg("topk_w"), py::arg("out"),
+        py::arg("T"), py::arg("D"), py::arg("k"), py::arg("ld_y"), py::arg("ld_out"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("moe_combine_workgroups", &gs::moe_combine_workgroups, py::arg("T"), py::arg("D"));
   // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once
   for (int k = 0; k < gs::kNumKnobs; ++k)
     m.def(("set_" + std::string(gs::kKnobs[k].name)).c_str(), [k](int value) { gs::set_knob(gs::Knob(k), value); });
