@@ -57,6 +57,12 @@ sized for the worst routing and the fraction of its workgroups that do work is d
 A thirteenth is "moe_combine" (LLM_MOE), the weighted scatter-back of the experts' outputs to token order
 (ops.loadgen.moe_combine): k indexed 16-byte-chunked row reads and k fused multiply-adds per output chunk -- a gather
 like the embedding bag's, but weighted, over rows the same step just wrote, no MFMA work.
+A fourteenth is "quant_mx" (LLM_MX), the quantiser of bf16 activations to block-scaled MX operands
+(ops.loadgen.quantize_mx): a stream like the SwiGLU's, 2 bytes in and 1 or 1/2 and a scale byte per 32 out, with a
+four-lane exponent maximum per block and integer / power-of-two arithmetic only, no MFMA work.
+A fifteenth is "gemm_mx" (LLM_MX), fp8 or fp4 activations on MXFP4 weights with one scale per 32 elements
+(ops.loadgen.gemm_mx): MFMA work at two or four times the bf16 rate on a quarter of the weight bytes -- at decode
+sizes bound by weight streaming like "moe_gemm", at prefill sizes by the matrix cores.
 """
 from __future__ import annotations
 
@@ -72,6 +78,10 @@ MOE_BLOCK_M = 64                  # rows of a tile of the MoE kernels' sorted la
 MOE_MAX_EXPERTS = 256             # ... the most experts ...
 MOE_MAX_TOP_K = 8                 # ... the most choices per token ...
 MOE_MAX_SLOTS = 32768             # ... and the most (token, choice) slots T * k of one routing (native/hip/moe_route.hip)
+
+
+MX_BLOCK = 32                     # elements of a row that share one scale byte of an MX operand (native/hip/quant_mx.hip)
+_MX_ELEMENT_BYTES = {"fp8": 1.0, "fp4": 0.5}
 
 
 def moe_max_tiles(T: int, k: int, E: int) -> int:
@@ -97,6 +107,8 @@ class Op:
     #                        | "moe_route" (MoE routing: top-k softmax of M tokens' N expert logits, the sorted tile layout)
     #                        | "moe_gemm" (bf16 grouped expert GEMM: the M * q routed rows times [N, K] weights of `rows` experts)
     #                        | "moe_combine" (bf16 weighted sum of each token's K expert output rows of N elements)
+    #                        | "quant_mx" (bf16 -> MX blocks of format `fmt`: M rows of N elements)
+    #                        | "gemm_mx" (MX GEMM, bf16 out: activations of format `fmt` on fp4 weights)
     M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu, sample: rows;
     #                        moe_route, moe_gemm, moe_combine: T, the tokens
     N: int = 0             # gather: D, the row length; attn, attn_split, prefill, rope_append: query heads;
@@ -114,6 +126,8 @@ class Op:
     splits: int = 0        # attn_split: kv_splits, workgroups per (sequence, KV head)
     gather: bool = False   # moe_gemm: A is the [T, K] token rows read through the permutation (the first projection);
     #                        False: A is the sorted [P_max, K] intermediate read in place (the down projection)
+    fmt: str = ""          # quant_mx: the MX element format written, "fp8" or "fp4"; gemm_mx: the activations' format
+    #                        (the weights are always "fp4")
 
     @property
     def is_gemm(self) -> bool:
@@ -122,7 +136,7 @@ class Op:
     @property
     def on_mfma(self) -> bool:
         """MFMA work in the roofline: costed max(flops term, bytes term), its flops on the MFMA side."""
-        return self.is_gemm or self.kind in ("prefill", "moe_gemm")
+        return self.is_gemm or self.kind in ("prefill", "moe_gemm", "gemm_mx")
 
     @property
     def flops(self) -> float:
@@ -147,6 +161,10 @@ class Op:
             return 2.0 * self.M * self.q * self.N * self.K
         if self.kind == "moe_combine":                            # a multiply-add per (token, choice, element)
             return 2.0 * self.M * self.K * self.N
+        if self.kind == "quant_mx":                               # per element: the exponent compare of the block maximum, the
+            return 5.0 * self.M * self.N                          # scaling multiply, the rounding add and subtract, the clamp
+        if self.kind == "gemm_mx":
+            return 2.0 * self.M * self.N * self.K
         return 2.0 * self.M * self.N * self.K if self.is_gemm else 2.0 * self.n_floats
 
     @property
@@ -190,10 +208,19 @@ class Op:
             return 2.0 * min(self.rows, slots) * self.N * self.K + 2.0 * slots * self.K + 2.0 * slots * self.N
         if self.kind == "moe_combine":                            # k rows of y per token, out, slot_pos and the weights
             return 2.0 * self.M * self.K * self.N + 2.0 * self.M * self.N + 8.0 * self.M * self.K
+        if self.kind == "quant_mx":                               # bf16 in, elements and one scale byte per 32 out
+            return (2.0 + _MX_ELEMENT_BYTES[self.fmt] + 1.0 / MX_BLOCK) * self.M * self.N
+        if self.kind == "gemm_mx":                                # elements and scales of both operands, bf16 out
+            return ((_MX_ELEMENT_BYTES[self.fmt] + 1.0 / MX_BLOCK) * self.M * self.K
+                    + (_MX_ELEMENT_BYTES["fp4"] + 1.0 / MX_BLOCK) * self.N * self.K + 2.0 * self.M * self.N)
         return 12.0 * self.n_floats
 
     def mfma_rate(self) -> float:
-        """MFMA throughput relative to bf16 (the fp8 MFMA does twice the work per clock)."""
+        """MFMA throughput relative to bf16 (the fp8 MFMA does twice the work per clock, the fp4 one four times; fp8
+        activations on fp4 weights are costed at the wider operand's rate: the mixed rate has not been measured
+        apart from the GEMM's, profiles/r16_mx/README.md)."""
+        if self.kind == "gemm_mx":
+            return 4.0 if self.fmt == "fp4" else 2.0
         return 2.0 if self.kind == "gemm8" else 1.0
 
     def workgroups(self, cu_budget: int) -> Optional[int]:
@@ -224,6 +251,10 @@ class Op:
             return default_moe_gemm_workgroups(self.M, self.q, self.rows, self.N)
         if self.kind == "moe_combine":
             return default_moe_combine_workgroups(self.M, self.N)
+        if self.kind == "quant_mx":
+            return default_quantize_mx_workgroups(self.M, self.N)
+        if self.kind == "gemm_mx":
+            return default_gemm_mx_workgroups(self.M, self.N, self.K, cu_budget)
         return None
 
 
@@ -461,9 +492,45 @@ LLM_MOE: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "quant_mx" and "gemm_mx" kinds, which those pinned tables do not list either: the decoder block of
+# LLM_BLOCK served QUANTISED -- every projection Op("gemm", r, N, K) of _llm_block becomes Op("quant_mx", r, K, fmt=f),
+# the activations' quantisation to MX blocks, followed by Op("gemm_mx", r, N, K, fmt=f) on MXFP4 weights (0.27 of the
+# bf16 bytes: 17 instead of 64 bytes per 32 elements).  The projections are, as there, 6144 x 4096 (QKV), 4096 x 4096
+# (output), 28672 x 4096 (gate / up) and 4096 x 14336 (down); norms, append, attention and SwiGLU stay bf16.  Each op
+# keeps its own operands, as everywhere in the executor.
+#   llm_mx_block_decode_256    f = "fp8": 256 rows of fp8 activations on fp4 weights -- the weight-bound case: the
+#                              GEMMs stream 12.8 to 59.5 MB of weights (bf16: 48 to 224 MiB) for 256 rows, the
+#                              quantisers are 128 or 448 workgroups.  The executor allocates two 1 GiB caches,
+#                              0.11 GiB of MX weights and 0.09 GiB of activations: 2.19 GiB, declared 2.25
+#   llm_mx_block_prefill_2048  f = "fp4": 2,048 rows, fp4 on fp4 -- the compute-bound case at four times the bf16 MFMA
+#                              rate; the quantisers read 16 or 56 MiB.  Two 32 MiB caches, the same weights and
+#                              0.68 GiB of activations: 0.85 GiB, declared 1.0
+# The quantiser and the MX GEMM are the fourteenth and fifteenth kernel characters; no co-run groups are measured
+# with them yet
+def _llm_mx_block(rows: int, f: str, append: Op, attention: Op) -> Tuple[Op, ...]:
+    ops: List[Op] = []
+    for o in _llm_block(rows, append, attention):
+        if o.kind == "gemm":
+            ops += [Op("quant_mx", o.M, o.K, fmt=f), Op("gemm_mx", o.M, o.N, o.K, relu=False, fmt=f)]
+        else:
+            ops.append(o)
+    return tuple(ops)
+
+
+LLM_MX: Dict[str, Workload] = {
+    "llm_mx_block_decode_256": Workload("llm_mx_block_decode_256", "llm_mx_block_decode", "hip", 256,
+                                        _llm_mx_block(256, "fp8", Op("rope_append", 256, 32, 1024, rows=8, q=1),
+                                                      Op("attn", 256, 32, 1024, rows=8)), 2.25),
+    "llm_mx_block_prefill_2048": Workload("llm_mx_block_prefill_2048", "llm_mx_block_prefill", "hip", 2048,
+                                          _llm_mx_block(2048, "fp4", Op("rope_append", 2, 32, 4096, rows=8, q=1024),
+                                                        Op("prefill", 2, 32, 4096, rows=8, q=1024)), 1.0),
+}
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head or LLM-MoE workload by exact name."""
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE):
+    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head, LLM-MoE or LLM-MX workload by exact
+    name."""
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX):
         w = table.get(name)
         if w is not None:
             return w
@@ -474,9 +541,9 @@ def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
     the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones, the LLM-block
-    ones, the LLM-head ones, the LLM-MoE ones last."""
+    ones, the LLM-head ones, the LLM-MoE ones, the LLM-MX ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE):
+    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX):
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]
@@ -643,6 +710,22 @@ def default_moe_combine_workgroups(T: int, D: int) -> int:
     workgroup, ceil(T * D / 2048) -- a pure-Python copy of moe_combine_workgroups (native/hip/moe_combine.hip),
     pinned like the above."""
     return -(-(T * (D // 8)) // MOE_COMBINE_CHUNKS_PER_WORKGROUP)
+
+
+QUANT_MX_CHUNKS_PER_WORKGROUP = 1024    # 16-byte input chunks per workgroup: 256 threads x 4 (native/hip/quant_mx.hip)
+
+
+def default_quantize_mx_workgroups(T: int, D: int) -> int:
+    """Workgroups the native MX quantiser launches: the work flattened over (row, 16-byte chunk of 8 inputs), 1,024
+    chunks per workgroup, ceil(T * D / 8192) -- a pure-Python copy of quantize_mx_workgroups (native/hip/quant_mx.hip),
+    pinned against it in tests/test_mx_cpu.py."""
+    return -(-(T * (D // 8)) // QUANT_MX_CHUNKS_PER_WORKGROUP)
+
+
+def default_gemm_mx_workgroups(M: int, N: int, K: int, cu_budget: int = 0) -> int:
+    """Workgroups the native MX GEMM launches: gemm_fp8's tiles under gemm_fp8's fill rule -- a pure-Python copy of
+    gemm_mx_workgroups (native/hip/gemm_mx.hip), pinned against it in tests/test_mx_cpu.py."""
+    return default_gemm_workgroups(M, N, K, cu_budget, fp8=True)
 
 
 def cu_fill(w: Workload, cu_budget: int = POD_CU_BUDGET) -> Optional[float]:

@@ -22,7 +22,10 @@ softmax, a 4-byte result; the caller supplies the uniforms); `moe_route(logits, 
 tile_expert, n_slots, gather_div=)` and `moe_combine(y, slot_pos, topk_w)` are the MLP of a mixture-of-experts block
 -- a top-k softmax and a counting sort of the (token, choice) slots by expert into 64-row tiles, a grouped GEMM with
 one weight matrix per tile (HBM-bound on the weights at decode sizes) and the weighted sum back to token order --
-and `moe_mlp` chains them around `swiglu`.  Shapes are validated on the host before launch (the kernels
+and `moe_mlp` chains them around `swiglu`; `quantize_mx(x, fmt)` turns bf16 activations into block-scaled MX
+operands (a memory-bound stream with a four-lane exponent maximum per block) and `gemm_mx(a_q, a_scales, w_q,
+w_scales, a_fmt)` multiplies fp8 or fp4 activations with fp4 weights on the block-scaled MFMA with real block
+scales (native/hip/quant_mx.hip, native/hip/gemm_mx.hip).  Shapes are validated on the host before launch (the kernels
 have no bounds checks by design).  On a GPU box the native module is mandatory: there is no PyTorch fallback
 path here (tests compare against torch fp32 / fp64 references instead).
 
@@ -150,7 +153,32 @@ kernels) rely on:
   * moe_combine: y bf16 [P_max, D] and out bf16 [T, D] under the same row rules, D a positive multiple of 8; topk_w
     fp32 [T, k] and slot_pos int32 [T * k], contiguous, 1 <= k <= 8; out disjoint from every input.  The kernel
     trusts slot_pos (moe_route wrote it): every entry names a row of y.  One thread per 16-byte output chunk
-    (models.workloads.default_moe_combine_workgroups).
+    (models.workloads.default_moe_combine_workgroups);
+  * THE MX FORMAT (quantize_mx, gemm_mx and their references; OCP Microscaling v1.0, block size 32 along the row,
+    K): a matrix [rows, K] is a pair (elements, scales).
+      - Scale: one E8M0 byte per (row, block), value 2^(b - 127); b = 255 is NaN.  uint8 [rows, K / 32], row stride in
+        elements.
+      - "fp4": e2m1 -- sign, 2 exponent bits, 1 mantissa bit; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6.  Two per byte,
+        element 2i in bits 3:0 of byte i: uint8 [rows, K / 2].  (The nibble order inside a block cannot change a dot
+        product of two fp4 operands as long as both use it; it is fixed so that bytes are comparable, and it is the
+        order in which the MFMA pairs fp4 elements with the bytes of an fp8 operand.)
+      - "fp8": OCP e4m3fn, one per byte: FP8 [rows, K].
+    The quantisation rule is integer and power-of-two arithmetic only, so the device and quantize_mx_reference agree
+    bit for bit.  Per block: e is the largest biased exponent field (bits >> 7) & 0xFF of the 32 bf16 inputs; emax
+    is 2 for fp4 and 8 for fp8.  e == 255 (an Inf or NaN in the block): scale byte 255, all element bytes of the
+    block 0x00.  Otherwise the scale byte is b = max(e - emax, 0), never above 253 (an all-zero and a
+    subnormal-amax block get b = 0), and an element is v * 2^(127 - b), exact in fp32, rounded to the element format
+    to nearest, ties to even, saturated at the largest finite magnitude (6 or 448); the input's sign bit is always
+    carried, so -0.0 and a negative value that rounds to zero give 0x8 or 0x80.  The rule is idempotent;
+  * quantize_mx (native/hip/quant_mx.hip): x under add_rmsnorm's row rules with D a positive multiple of 32; q and
+    scales with contiguous rows and any row stride >= the row, pairwise disjoint and disjoint from x.  The grid rule
+    -- the work flattened over (row, 16-byte chunk of 8 inputs), 1,024 chunks per workgroup: ceil(T * D / 8192)
+    workgroups -- is part of the contract (models.workloads.default_quantize_mx_workgroups);
+  * gemm_mx (native/hip/gemm_mx.hip): M, N multiples of 64, K of 128; element rows 16-byte aligned (row stride a
+    multiple of 16 bytes); scale rows any stride >= K / 32; C and bias as the other GEMMs'.  Tiles and fill rule are
+    gemm_fp8's (models.workloads.default_gemm_mx_workgroups).  fp32 accumulation inside the scaled MFMA (one
+    instruction per 128 k, its internal adder undocumented: tests/test_gpu_gemm_mx_exact.py measures it), K tiles
+    summed in order, one rounding to bf16; no split-K, no atomics, launches repeat bit for bit.
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -1344,6 +1372,203 @@ def moe_mlp(x: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, w2:
     swiglu(ws["h13"], out=ws["act"], stream=stream)
     moe_gemm(ws["act"], w2, sorted_ids, tile_expert, n, gather_div=0, out=ws["y"], stream=stream, check=False)
     return moe_combine(ws["y"], slot_pos, topk_w, out=out, stream=stream)
+
+
+# ------------------------------------------------------------------------------------------------ MX operands
+MX_BLOCK = 32                                             # elements of a row that share one scale byte
+MX_FORMATS = ("fp8", "fp4")
+_MX_EMAX = {"fp8": 8, "fp4": 2}                           # exponent of the largest finite magnitude: 448 = 1.75 * 2^8, 6 = 1.5 * 2^2
+_MX_MANT = {"fp8": 3, "fp4": 1}                           # mantissa bits
+_MX_EMIN = {"fp8": -6, "fp4": 0}                          # exponent of the smallest normal magnitude
+_MX_MAX_CODE = {"fp8": 0x7E, "fp4": 0x7}                  # the code of the largest finite magnitude (0x7F is fp8's NaN)
+_MX_SIGN_SHIFT = {"fp8": 7, "fp4": 3}
+_FP4_MAGNITUDES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _mx_fmt(name: str, fmt) -> str:
+    if fmt not in MX_FORMATS:
+        raise ValueError(f"{name}: fmt = {fmt!r} must be one of {MX_FORMATS}")
+    return fmt
+
+
+def _mx_code(fmt: str) -> int:
+    """The native layer's code of a format: the MFMA's cbsz / blgp value (api.h kMxFp8 / kMxFp4)."""
+    return 0 if fmt == "fp8" else 4
+
+
+def mx_element_dtype(fmt: str) -> torch.dtype:
+    return FP8 if _mx_fmt("mx_element_dtype", fmt) == "fp8" else torch.uint8
+
+
+def mx_row_bytes(fmt: str, K: int) -> int:
+    """Bytes (= array elements) of a row of K MX elements."""
+    return K if _mx_fmt("mx_row_bytes", fmt) == "fp8" else K // 2
+
+
+def quantize_mx_reference(x: torch.Tensor, fmt: str):
+    """THE quantisation rule of the MX operands (the module docstring states the format) on the CPU, in integer torch
+    ops only: x bf16 [T, D], D a multiple of 32 -> (q, scales) as quantize_mx gives them, bit for bit.  Per block of
+    32: e = the largest exponent field (bits >> 7) & 0xFF; e == 255 gives scale byte 255 and element bytes 0x00;
+    otherwise b = max(e - emax, 0) and an element is v * 2^(127 - b) rounded to the element format to nearest, ties to
+    even, saturated at 448 / 6, the sign bit always carried.  The rounding is done on the 8-bit significand: with
+    sig * 2^p the exact scaled magnitude, L = floor(log2) of it and the format's step 2^(max(L, emin) - M) at it,
+    k = RNE(sig * 2^p / step) and the code is ((L - emin + 1) << M) + k - 2^M for L >= emin, else k -- a rounding
+    carry walks into the exponent by itself -- capped at the code of the largest finite magnitude."""
+    _mx_fmt("quantize_mx_reference", fmt)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.shape[1] % MX_BLOCK or x.is_cuda:
+        raise ValueError("quantize_mx_reference expects a CPU bf16 [T, D] tensor with D a multiple of 32")
+    T, D = x.shape
+    M, emin, emax = _MX_MANT[fmt], _MX_EMIN[fmt], _MX_EMAX[fmt]
+    bits = x.contiguous().view(torch.int16).to(torch.int64) & 0xFFFF
+    sign, E, m = bits >> 15, (bits >> 7) & 0xFF, bits & 0x7F
+    e = E.view(T, D // MX_BLOCK, MX_BLOCK).amax(dim=2)                  # [T, D / 32]
+    nonfinite = e == 255
+    b = torch.where(nonfinite, torch.full_like(e, 255), (e - emax).clamp(min=0))
+    bb = b.clamp(max=253).repeat_interleave(MX_BLOCK, dim=1)            # per element
+    sig = m + (E > 0).to(torch.int64) * 128                              # |v| = sig * 2^(max(E, 1) - 134)
+    p = E.clamp(min=1) - 134 + 127 - bb                                  # scaled magnitude = sig * 2^p
+    bitlen = sum((sig >= (1 << i)).to(torch.int64) for i in range(8))
+    L = p + bitlen - 1                                                   # floor(log2), meaningless for sig == 0
+    s = torch.maximum(L, torch.full_like(L, emin)) - M - p               # the step is 2^(p + s)
+    down = s.clamp(min=1, max=16)                                        # s > 0: k = RNE(sig / 2^s); sig < 2^8
+    k_down = (sig + (torch.ones_like(down) << (down - 1)) - 1 + ((sig >> down) & 1)) >> down
+    k_up = sig << (-s).clamp(min=0, max=M)                               # s <= 0: exact
+    k = torch.where(s > 0, k_down, k_up)
+    code = torch.where(L >= emin, ((L - emin + 1) << M) + k - (1 << M), k)
+    code = torch.where(sig == 0, torch.zeros_like(code), code).clamp(max=_MX_MAX_CODE[fmt])
+    code = code | (sign << _MX_SIGN_SHIFT[fmt])
+    code = torch.where(nonfinite.repeat_interleave(MX_BLOCK, dim=1), torch.zeros_like(code), code)
+    if fmt == "fp8":
+        q = code.to(torch.uint8).view(FP8)
+    else:
+        q = (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8)
+    return q, b.to(torch.uint8)
+
+
+def dequantize_mx_reference(q: torch.Tensor, scales: torch.Tensor, fmt: str) -> torch.Tensor:
+    """The values an MX operand (q, scales) stands for, float64 [rows, K], on the CPU: element * 2^(b - 127), a block
+    with scale byte 255 all NaN.  Every finite result is exact in float64."""
+    _mx_fmt("dequantize_mx_reference", fmt)
+    if q.is_cuda or scales.is_cuda or q.dim() != 2 or scales.dim() != 2 or scales.dtype != torch.uint8:
+        raise ValueError("dequantize_mx_reference expects CPU 2-D q and uint8 scales")
+    if fmt == "fp8":
+        if q.dtype not in (FP8, torch.uint8):
+            raise ValueError("dequantize_mx_reference: fp8 elements are float8_e4m3fn (or their bytes as uint8)")
+        el = (q.view(FP8) if q.dtype == torch.uint8 else q).to(torch.float32).to(torch.float64)
+    else:
+        if q.dtype != torch.uint8:
+            raise ValueError("dequantize_mx_reference: fp4 elements are packed in uint8")
+        lut = torch.tensor(_FP4_MAGNITUDES + tuple(-v for v in _FP4_MAGNITUDES), dtype=torch.float64)
+        qi = q.to(torch.int64)
+        el = torch.stack((lut[qi & 0xF], lut[qi >> 4]), dim=2).reshape(q.shape[0], 2 * q.shape[1])
+    rows, K = el.shape
+    if K % MX_BLOCK or tuple(scales.shape) != (rows, K // MX_BLOCK):
+        raise ValueError(f"dequantize_mx_reference: scales {tuple(scales.shape)} do not match {rows} x {K} elements")
+    b = scales.to(torch.int64)
+    factor = torch.ldexp(torch.ones((), dtype=torch.float64), b - 127)
+    factor = torch.where(b == 255, torch.full_like(factor, float("nan")), factor)
+    return el * factor.repeat_interleave(MX_BLOCK, dim=1)
+
+
+def _mx_rows(name: str, nm: str, t: torch.Tensor, dtype: torch.dtype, rows: Optional[int], cols: int,
+             align: int) -> int:
+    """The checks of a 2-D byte operand (MX elements or scales): dtype, [rows, cols], contiguous rows, a row stride
+    >= cols and a multiple of `align` bytes, the first element `align`-byte aligned.  Returns the row stride."""
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: {nm} must be {dtype} (got {t.dtype})")
+    if t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{name}: {nm} must be [{'rows' if rows is None else rows}, {cols}] (got {tuple(t.shape)})")
+    n = t.shape[0]
+    if cols > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: {nm} must have contiguous rows")
+    if n > 1 and (t.stride(0) < cols or t.stride(0) % align):
+        raise ValueError(f"{name}: {nm} row stride {t.stride(0)} must be >= {cols}"
+                         + (f" and a multiple of {align}" if align > 1 else ""))
+    if t.data_ptr() % align:
+        raise ValueError(f"{name}: {nm} must be {align}-byte aligned")
+    return _row_stride(t, n, cols)
+
+
+def quantize_mx(x: torch.Tensor, fmt: str, *, out: Optional[torch.Tensor] = None,
+                scales: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """x bf16 [T, D], D a multiple of 32 -> (q, scales) in the MX format `fmt` ("fp8" or "fp4"; the module docstring
+    states format and rule; quantize_mx_reference is the same rule on the CPU, bit for bit).  q (`out`) is
+    float8_e4m3fn [T, D] or uint8 [T, D / 2], scales uint8 [T, D / 32]; both are made when None, may be row-strided
+    views (any row stride >= the row; 8-byte / 4-byte aligned q rows get one store per lane, others byte stores) and
+    have every byte of their windows written.  x follows add_rmsnorm's row rules.  No operand may overlap another.
+    Nothing here reads device data: the launch can be captured into a graph, and replays give the same bytes.
+    T == 0 launches nothing."""
+    name = "quantize_mx"
+    _mx_fmt(name, fmt)
+    _check_devices(name, x, out, scales)
+    if x.dim() == 2 and (x.shape[1] < MX_BLOCK or x.shape[1] % MX_BLOCK):
+        raise ValueError(f"{name}: D = {x.shape[1]} must be a positive multiple of {MX_BLOCK}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: x must be bf16 (got {x.dtype})")
+    ld_x = _bf16_rows(name, "x", x)
+    T, D = x.shape
+    if T * (D // 8) >= 2 ** 31 * 1024:
+        raise ValueError(f"{name}: more than 2^31 - 1 workgroups")
+    if out is None:
+        out = torch.empty((T, mx_row_bytes(fmt, D)), dtype=mx_element_dtype(fmt), device=x.device)
+    if scales is None:
+        scales = torch.empty((T, D // MX_BLOCK), dtype=torch.uint8, device=x.device)
+    ld_q = _mx_rows(name, "out", out, mx_element_dtype(fmt), T, mx_row_bytes(fmt, D), 1)
+    ld_s = _mx_rows(name, "scales", scales, torch.uint8, T, D // MX_BLOCK, 1)
+    for (na, ta), (nb, tb) in ((("out", out), ("x", x)), (("scales", scales), ("x", x)), (("out", out), ("scales", scales))):
+        if _overlap(ta, tb):
+            raise ValueError(f"{name}: {na} overlaps {nb}")
+    if T == 0:
+        return out, scales
+    h = _native.hip()
+    with torch.cuda.device(x.device):
+        h.quantize_mx_bf16(x.data_ptr(), out.data_ptr(), scales.data_ptr(), T, D, ld_x, ld_q, ld_s, _mx_code(fmt),
+                           _stream_ptr(stream, x.device))
+    return out, scales
+
+
+def gemm_mx(a_q: torch.Tensor, a_scales: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, a_fmt: str, *,
+            out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, relu: bool = False,
+            stream: Optional[torch.cuda.Stream] = None, cu_budget: int = 0) -> torch.Tensor:
+    """out[M, N] = act(A[M, K] @ W[N, K]^T + bias[N]) -- both operands MX (elements, scales) pairs (the module
+    docstring states the format): W always "fp4" (w_q uint8 [N, K / 2]), A of format a_fmt: "fp8" (a_q float8_e4m3fn
+    [M, K]) or "fp4" (a_q uint8 [M, K / 2]); scales uint8 [rows, K / 32].  fp32 accumulate on the block-scaled MFMA,
+    bf16 out.  M, N multiples of 64, K of 128.  Element rows are 16-byte aligned (row stride a multiple of 16, the
+    first element 16-byte aligned); scale rows may have any row stride >= K / 32; out, bias, relu and cu_budget as
+    gemm_fp8.  out may not overlap an operand.  Scale byte 255 and scale byte 0 under non-zero elements are outside
+    the contract; a block of zero elements with scale byte 0 contributes exactly 0.  Nothing here reads device data:
+    the launch can be captured into a graph."""
+    name = "gemm_mx"
+    _mx_fmt(name, a_fmt)
+    _check_devices(name, a_q, a_scales, w_q, w_scales, out, bias)
+    if a_q.dim() != 2 or w_q.dim() != 2:
+        raise ValueError(f"{name}: a_q and w_q must be 2-D (got {tuple(a_q.shape)} and {tuple(w_q.shape)})")
+    M, N, K = a_q.shape[0], w_q.shape[0], 2 * w_q.shape[1]
+    check_gemm_shapes(M, N, K, 128, name)
+    lda = _mx_rows(name, "a_q", a_q, mx_element_dtype(a_fmt), M, mx_row_bytes(a_fmt, K), 16)
+    ldw = _mx_rows(name, "w_q", w_q, torch.uint8, N, K // 2, 16)
+    ld_as = _mx_rows(name, "a_scales", a_scales, torch.uint8, M, K // MX_BLOCK, 1)
+    ld_ws = _mx_rows(name, "w_scales", w_scales, torch.uint8, N, K // MX_BLOCK, 1)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a_q.device)
+    if (out.dim() != 2 or tuple(out.shape) != (M, N) or out.dtype != torch.bfloat16 or out.stride(1) != 1
+            or out.stride(0) < N or out.stride(0) % 4 or out.data_ptr() % 8):
+        raise ValueError(f"{name}: out must be bf16 [{M}, {N}] with contiguous, 8-byte aligned rows")
+    bptr = 0
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() != N or not bias.is_contiguous() \
+                or bias.data_ptr() % 16:
+            raise ValueError(f"{name}: bias must be a contiguous, 16-byte aligned fp32 vector of length N = {N}")
+        bptr = bias.data_ptr()
+    for nm, t in (("a_q", a_q), ("a_scales", a_scales), ("w_q", w_q), ("w_scales", w_scales), ("bias", bias)):
+        if t is not None and _overlap(out, t):
+            raise ValueError(f"{name}: out overlaps {nm}")
+    h = _native.hip()
+    with torch.cuda.device(a_q.device):
+        h.gemm_mx_nt(a_q.data_ptr(), a_scales.data_ptr(), w_q.data_ptr(), w_scales.data_ptr(), out.data_ptr(), bptr,
+                     M, N, K, lda, ld_as, ldw, ld_ws, out.stride(0), _mx_code(a_fmt), bool(relu),
+                     _stream_ptr(stream, a_q.device), cu_budget)
+    return out
 
 
 def gemm_flops(M: int, N: int, K: int) -> float:

@@ -225,6 +225,39 @@ def _moe_combine_operands(o: Op, g: torch.Generator, device: torch.device) -> tu
     return torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device), y, slot_pos.to(device), w.to(device)
 
 
+def _quant_mx_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(q, scales, x): M rows of N elements, randn in bf16, and the MX outputs of format o.fmt."""
+    x = torch.randn(o.M, o.N, generator=g).to(torch.bfloat16).to(device)
+    q = torch.empty(o.M, loadgen.mx_row_bytes(o.fmt, o.N), dtype=loadgen.mx_element_dtype(o.fmt), device=device)
+    return q, torch.empty(o.M, o.N // loadgen.MX_BLOCK, dtype=torch.uint8, device=device), x
+
+
+MX_PATTERN_ROWS = 256             # rows of the CPU-generated block an MX weight matrix repeats
+
+
+def _mx_random(rows: int, K: int, fmt: str, g: torch.Generator, device: torch.device) -> tuple:
+    """(elements, scales) of a [rows, K] MX operand made without quantising anything: random element bytes -- for fp8
+    without the two NaN codes 0x7F and 0xFF (the low seven bits are drawn from [0, 0x7F)) -- and scale bytes from
+    [120, 127].  A matrix of more than MX_PATTERN_ROWS rows repeats one CPU-generated block of that many."""
+    n = min(rows, MX_PATTERN_ROWS)
+    if fmt == "fp8":
+        el = torch.randint(0, 0x7F, (n, K), generator=g) | (torch.randint(0, 2, (n, K), generator=g) << 7)
+    else:
+        el = torch.randint(0, 256, (n, K // 2), generator=g)
+    sc = torch.randint(120, 128, (n, K // loadgen.MX_BLOCK), generator=g).to(torch.uint8)
+    el = _repeat(el.to(torch.uint8).to(device), rows).view(loadgen.mx_element_dtype(fmt))
+    return el, _repeat(sc.to(device), rows)
+
+
+def _gemm_mx_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(c, a_q, a_scales, w_q, w_scales, bias): activations [M, K] of format o.fmt, fp4 weights [N, K] (_mx_random),
+    a zero bias and the bf16 output."""
+    a_q, a_s = _mx_random(o.M, o.K, o.fmt, g, device)
+    w_q, w_s = _mx_random(o.N, o.K, "fp4", g, device)
+    bias = torch.zeros(o.N, dtype=torch.float32, device=device)
+    return torch.empty(o.M, o.N, dtype=torch.bfloat16, device=device), a_q, a_s, w_q, w_s, bias
+
+
 def _triad_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return tuple(torch.ones(o.n_floats, dtype=torch.float32, device=device) for _ in range(3))
 
@@ -301,6 +334,16 @@ def _launch_moe_combine(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.moe_combine(y, slot_pos, topk_w, out=out, stream=st)
 
 
+def _launch_quant_mx(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    q, scales, x = t
+    loadgen.quantize_mx(x, o.fmt, out=q, scales=scales, stream=st)
+
+
+def _launch_gemm_mx(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    c, a_q, a_s, w_q, w_s, bias = t
+    loadgen.gemm_mx(a_q, a_s, w_q, w_s, o.fmt, out=c, bias=bias, relu=o.relu, stream=st, cu_budget=budget)
+
+
 def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     x, y, z = t
     loadgen.triad(x, y, z, 1.0001, blocks=blocks, stream=st)
@@ -313,8 +356,8 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # attn_split the same and the workspace; rope_append (q_out, qkv, cos_sin, k_cache, v_cache, table, ctx,
 # q_start); add_rmsnorm (y, res_out, x, residual, weight); swiglu (out, gate_up); sample (out, logits, u,
 # temperature, top_k, top_p); moe_route (topk_ids, logits, topk_w, sorted_ids, tile_expert, expert_offsets,
-# slot_pos); moe_gemm (out, a, w, sorted_ids, tile_expert); moe_combine (out, y, slot_pos, topk_w); triad (x, y, z),
-# x = y + s z.
+# slot_pos); moe_gemm (out, a, w, sorted_ids, tile_expert); moe_combine (out, y, slot_pos, topk_w); quant_mx (q, scales,
+# x); gemm_mx (c, a_q, a_scales, w_q, w_scales, bias); triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -329,6 +372,8 @@ OP_KINDS = {
     "moe_route": (_moe_route_operands, _launch_moe_route, 0),
     "moe_gemm": (_moe_gemm_operands, _launch_moe_gemm, 0),
     "moe_combine": (_moe_combine_operands, _launch_moe_combine, 0),
+    "quant_mx": (_quant_mx_operands, _launch_quant_mx, 0),
+    "gemm_mx": (_gemm_mx_operands, _launch_gemm_mx, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -129,6 +129,34 @@ void moe_combine_bf16(uintptr_t y, uintptr_t slot_pos, uintptr_t topk_w, uintptr
                       int64_t ld_out, uintptr_t stream);
 // workgroups of that launch: one thread per 16-byte output chunk, ceil(T * D / 2048)
 int moe_combine_workgroups(int T, int D);
+// MX operands -- native/hip/quant_mx.hip, gemm_mx.hip.  THE FORMAT (OCP Microscaling v1.0, block size 32 along the
+// row): a matrix [rows, K], K a multiple of 32, is a pair (elements, scales).  scales: uint8 [rows, K / 32], one E8M0
+// byte per (row, block), value 2^(b - 127), b = 255 is NaN.  elements, by format code (the MFMA's cbsz / blgp codes):
+//   kMxFp4 = 4  e2m1 (sign, 2 exponent bits, 1 mantissa bit: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6), two per byte,
+//               element 2i in bits 3:0 of byte i: uint8 [rows, K / 2]
+//   kMxFp8 = 0  OCP e4m3fn, one per byte: [rows, K]
+// All row strides are in elements of the array they belong to (bytes, here).  THE QUANTISATION RULE, per block of 32
+// bf16 inputs: e = the largest biased exponent field (bits >> 7) & 0xFF; emax = 2 (fp4) / 8 (fp8).  e == 255 (an Inf
+// or NaN in the block): scale byte 255 and every element byte of the block 0x00.  Otherwise the scale byte is
+// b = max(e - emax, 0) (at most 252; an all-zero or subnormal-amax block gets 0) and an element is v * 2^(127 - b),
+// rounded to the element format to nearest, ties to even, saturated at the largest finite magnitude (6 / 448), the
+// input's sign bit always carried (-0.0, and a negative value that rounds to zero, give 0x8 / 0x80).
+constexpr int kMxFp8 = 0, kMxFp4 = 4;
+// x bf16 [T, D] (D a multiple of 32, 16-byte aligned rows) -> q and scales of format fmt, every scale byte written;
+// no overlap; T == 0 launches nothing
+void quantize_mx_bf16(uintptr_t x, uintptr_t q, uintptr_t scales, int T, int D, int64_t ld_x, int64_t ld_q,
+                      int64_t ld_scales, int fmt, uintptr_t stream);
+// workgroups of that launch: one per 1,024 16-byte input chunks of the flattened (row, chunk) space, ceil(T * D / 8192)
+int quantize_mx_workgroups(int T, int D);
+// c[m, n] = act(sum_k a[m, k] w[n, k] + bias[n]), bf16 out: a of format a_fmt (kMxFp8 or kMxFp4), w always kMxFp4;
+// M, N multiples of 64, K of 128; element rows 16-byte aligned; bias fp32, relu and cu_budget as gemm_fp8_nt
+void gemm_mx_nt(uintptr_t a, uintptr_t a_scales, uintptr_t w, uintptr_t w_scales, uintptr_t c, uintptr_t bias, int M,
+                int N, int K, int lda, int ld_a_scales, int ldw, int ld_w_scales, int ldc, int a_fmt, bool relu,
+                uintptr_t stream, int cu_budget);
+// workgroups of that launch: gemm_fp8_nt's tiles and fill rule (fp8_tile_128)
+int gemm_mx_workgroups(int M, int N, int K, int cu_budget);
+// the fill rule of gemm_fp8_nt and gemm_mx_nt (gemm.hip): 128 x 128 tiles, else 64 x 64
+bool fp8_tile_128(int M, int N, int cu_budget);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

@@ -118,6 +118,18 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("T"), py::arg("D"), py::arg("k"), py::arg("ld_y"), py::arg("ld_out"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
   m.def("moe_combine_workgroups", &gs::moe_combine_workgroups, py::arg("T"), py::arg("D"));
+  m.attr("MX_FP8") = gs::kMxFp8;
+  m.attr("MX_FP4") = gs::kMxFp4;
+  m.def("quantize_mx_bf16", &gs::quantize_mx_bf16, py::arg("x"), py::arg("q"), py::arg("scales"), py::arg("T"),
+        py::arg("D"), py::arg("ld_x"), py::arg("ld_q"), py::arg("ld_scales"), py::arg("fmt"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("quantize_mx_workgroups", &gs::quantize_mx_workgroups, py::arg("T"), py::arg("D"));
+  m.def("gemm_mx_nt", &gs::gemm_mx_nt, py::arg("a"), py::arg("a_scales"), py::arg("w"), py::arg("w_scales"),
+        py::arg("c"), py::arg("bias"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ld_a_scales"),
+        py::arg("ldw"), py::arg("ld_w_scales"), py::arg("ldc"), py::arg("a_fmt"), py::arg("relu"), py::arg("stream"),
+        py::arg("cu_budget") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def("gemm_mx_workgroups", &gs::gemm_mx_workgroups, py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("cu_budget") = 0);
   // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once
   for (int k = 0; k < gs::kNumKnobs; ++k)
     m.def(("set_" + std::string(gs::kKnobs[k].name)).c_str(), [k](int value) { gs::set_knob(gs::Knob(k), value); });

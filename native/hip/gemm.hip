@@ -318,7 +318,7 @@ static int resolve_gemm_tile(int M, int N, int K, int cu_budget) {
 
 // fp8 fill rule, as the bf16 picker: 128x128 when it gives every CU of the budget a block (two
 // for a lone kernel), else 64x64
-static bool fp8_tile_128(int M, int N, int cu_budget) {
+bool fp8_tile_128(int M, int N, int cu_budget) {
   return fills<128, 128>(M, N, whole_chip(cu_budget) ? 2 * kCus : cu_budget);
 }
 
