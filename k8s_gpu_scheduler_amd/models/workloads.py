@@ -63,6 +63,11 @@ four-lane exponent maximum per block and integer / power-of-two arithmetic only,
 A fifteenth is "gemm_mx" (LLM_MX), fp8 or fp4 activations on MXFP4 weights with one scale per 32 elements
 (ops.loadgen.gemm_mx): MFMA work at two or four times the bf16 rate on a quarter of the weight bytes -- at decode
 sizes bound by weight streaming like "moe_gemm", at prefill sizes by the matrix cores.
+A sixteenth to eighteenth are "rope_append_kv8", "attn_kv8" and "attn_split_kv8" (LLM_KV8): the append and the two decode
+attentions over an FP8 (OCP e4m3fn) paged cache with one fp32 scale per KV head (ops.loadgen.rope_append and
+paged_decode_attention_kv8) -- the attentions stream HALF the cache bytes of "attn" / "attn_split"
+for the same flops, at the cost of a byte -> bf16 conversion in front of every MFMA operand, and hold twice the
+sequences per GiB; the append rounds every K and V element with an IEEE division and a few integer operations.
 """
 from __future__ import annotations
 
@@ -107,6 +112,8 @@ class Op:
     #                        | "moe_route" (MoE routing: top-k softmax of M tokens' N expert logits, the sorted tile layout)
     #                        | "moe_gemm" (bf16 grouped expert GEMM: the M * q routed rows times [N, K] weights of `rows` experts)
     #                        | "moe_combine" (bf16 weighted sum of each token's K expert output rows of N elements)
+    #                        | "rope_append_kv8", "attn_kv8", "attn_split_kv8" ("rope_append", "attn", "attn_split" over an FP8
+    #                          e4m3fn cache with one fp32 scale per KV head; the fields of their bf16 kinds)
     #                        | "quant_mx" (bf16 -> MX blocks of format `fmt`: M rows of N elements)
     #                        | "gemm_mx" (MX GEMM, bf16 out: activations of format `fmt` on fp4 weights)
     M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu, sample: rows;
@@ -142,12 +149,12 @@ class Op:
     def flops(self) -> float:
         if self.kind == "gather":
             return 1.0 * self.M * self.K * self.N                 # one add per gathered element
-        if self.kind in ("attn", "attn_split"):                   # q . K^T and P . V, a multiply-add each
+        if self.kind in ("attn", "attn_split", "attn_kv8", "attn_split_kv8"):      # q . K^T and P . V, a multiply-add each
             return 4.0 * self.M * self.N * self.K * ATTN_HEAD_DIM
         if self.kind == "prefill":                                # the same per (query, token at or below it) pair:
             pairs = self.q * (self.K - self.q) + self.q * (self.q + 1) / 2        # the prefix, then the causal triangle
             return 4.0 * ATTN_HEAD_DIM * self.M * self.N * pairs
-        if self.kind == "rope_append":                            # two multiplies and one add per rotated element of q and K
+        if self.kind in ("rope_append", "rope_append_kv8"):       # two multiplies and one add per rotated element of q and K
             return 3.0 * ATTN_HEAD_DIM * (self.N + self.rows) * self.M * self.q
         if self.kind == "add_rmsnorm":                            # the add, the square and its sum, the two multiplies
             return 5.0 * self.M * self.N
@@ -175,24 +182,27 @@ class Op:
             return 1.0 * (self.M * self.K + self.N * self.K) + 2.0 * self.M * self.N
         if self.kind == "gather":                                 # rows read, indices, offsets, output
             return 2.0 * self.M * self.K * self.N + 4.0 * self.M * self.K + 4.0 * (self.M + 1) + 2.0 * self.M * self.N
-        if self.kind in ("attn", "attn_split"):                   # K and V, q and out, block table, ctx_lens
-            b = (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.N * ATTN_HEAD_DIM
-                 + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M)
-            if self.kind == "attn_split":                         # the fp32 workspace, written and read once
+        if self.kind in ("attn", "attn_split", "attn_kv8", "attn_split_kv8"):      # K and V, q and out, block table, ctx_lens
+            kv8 = self.kind.endswith("_kv8")                      # 1-byte K / V elements and the two [Hkv] fp32 scale vectors
+            b = ((2.0 if kv8 else 4.0) * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.N * ATTN_HEAD_DIM
+                 + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + (8.0 * self.rows if kv8 else 0.0))
+            if self.kind.startswith("attn_split"):                # the fp32 workspace, written and read once
                 b += 2 * 4.0 * decode_split_workspace_floats(self.M, self.N, self.splits)
             return b
         if self.kind == "prefill":                                # K and V read once, q and out, table, ctx_lens, q_start
             return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.q * self.N * ATTN_HEAD_DIM
                     + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + 4.0 * (self.M + 1))
-        if self.kind == "rope_append":
+        if self.kind in ("rope_append", "rope_append_kv8"):
+            kv8 = self.kind == "rope_append_kv8"                  # 1-byte K / V elements and the two [Hkv] fp32 scale vectors
             tokens = self.M * self.q
             # table entries (K - q) // 32 .. (K - 1) // 32 of each sequence
             touched = (self.K - 1) // ATTN_BLOCK_TOKENS - (self.K - self.q) // ATTN_BLOCK_TOKENS + 1 if self.q else 0
             return (2.0 * tokens * (self.N + 2 * self.rows) * ATTN_HEAD_DIM        # qkv read
                     + 2.0 * tokens * self.N * ATTN_HEAD_DIM                        # q_out written
-                    + 2.0 * tokens * 2 * self.rows * ATTN_HEAD_DIM                 # K and V written
+                    + (1.0 if kv8 else 2.0) * tokens * 2 * self.rows * ATTN_HEAD_DIM      # K and V written
                     + 4.0 * ATTN_HEAD_DIM * tokens                                 # one 512-byte cos / sin row per token
-                    + 4.0 * self.M + 4.0 * (self.M + 1) + 4.0 * self.M * touched)  # ctx_lens, q_start, the touched table entries
+                    + 4.0 * self.M + 4.0 * (self.M + 1) + 4.0 * self.M * touched   # ctx_lens, q_start, the touched table entries
+                    + (8.0 * self.rows if kv8 else 0.0))
         if self.kind == "add_rmsnorm":                            # x and residual read, residual_out and y written, the weight
             return 8.0 * self.M * self.N + 2.0 * self.N
         if self.kind == "swiglu":                                 # gate and up read, out written
@@ -231,13 +241,13 @@ class Op:
             return default_gemm_workgroups(self.M, self.N, self.K, cu_budget, self.kind == "gemm8")
         if self.kind == "gather":
             return default_gather_workgroups(self.M)
-        if self.kind == "attn":
+        if self.kind in ("attn", "attn_kv8"):
             return default_attn_workgroups(self.M, self.rows)
         if self.kind == "prefill":
             return default_prefill_workgroups(self.M, self.N, self.rows, self.q)
-        if self.kind == "attn_split":
+        if self.kind in ("attn_split", "attn_split_kv8"):
             return default_attn_split_workgroups(self.M, self.rows, self.splits)
-        if self.kind == "rope_append":
+        if self.kind in ("rope_append", "rope_append_kv8"):
             return default_rope_append_workgroups(self.M, self.rows, self.q)
         if self.kind == "add_rmsnorm":
             return default_add_rmsnorm_workgroups(self.M)
@@ -527,10 +537,35 @@ LLM_MX: Dict[str, Workload] = {
 }
 
 
+# Workloads of the "rope_append_kv8", "attn_kv8" and "attn_split_kv8" kinds, which those pinned tables do not list either:
+# the attention half of a decoder layer served from an FP8 (e4m3fn) paged KV cache with one fp32 scale per KV head.  Each
+# op keeps its own operands, as everywhere in the executor: the append writes one cache and the attention reads another.
+#   llm_kv8_layer_decode_256  llm_layer_decode_256 with the two kv8 kinds: the append quantises 256 x 8 K rows and V
+#                             columns into slot 31 of their blocks, the attention streams 512 MiB instead of 1 GiB.  The
+#                             executor allocates two 512 MiB caches (K + V each) and 0.10 GiB of GEMM and qkv operands:
+#                             1.10 GiB, declared 1.25
+#   llm_kv8_decode_long_8     llm_decode_long_8 with the append of the 8 new tokens in front of the split-KV attention
+#                             (splits = 4, as there): 64 x 6144 x 4096, rope_append_kv8, attn_split_kv8, 64 x 4096 x 4096.
+#                             Two 512 MiB caches and 0.10 GiB of other operands (the 16 MiB rope table among them):
+#                             1.10 GiB, declared 1.25
+# They are the sixteenth to eighteenth kernel characters; no co-run groups are measured with them yet
+LLM_KV8: Dict[str, Workload] = {
+    "llm_kv8_layer_decode_256": Workload("llm_kv8_layer_decode_256", "llm_kv8_layer_decode", "hip", 256,
+                                         (Op("gemm", 256, 6144, 4096), Op("rope_append_kv8", 256, 32, 1024, rows=8, q=1),
+                                          Op("attn_kv8", 256, 32, 1024, rows=8), Op("gemm", 256, 4096, 4096)), 1.25),
+    "llm_kv8_decode_long_8": Workload("llm_kv8_decode_long_8", "llm_kv8_decode_long", "hip", 8,
+                                      (Op("gemm", 64, 6144, 4096), Op("rope_append_kv8", 8, 32, 32768, rows=8, q=1),
+                                       Op("attn_split_kv8", 8, 32, 32768, rows=8, splits=4),
+                                       Op("gemm", 64, 4096, 4096)), 1.25),
+}
+
+_TABLES = (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX, LLM_KV8)
+
+
 def get(name: str) -> Workload:
-    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head, LLM-MoE or LLM-MX workload by exact
-    name."""
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX):
+    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head, LLM-MoE, LLM-MX or LLM-KV8 workload by
+    exact name."""
+    for table in _TABLES:
         w = table.get(name)
         if w is not None:
             return w
@@ -541,9 +576,9 @@ def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
     the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones, the LLM-block
-    ones, the LLM-head ones, the LLM-MoE ones, the LLM-MX ones last."""
+    ones, the LLM-head ones, the LLM-MoE ones, the LLM-MX ones, the LLM-KV8 ones last."""
     nm = pod_name.replace("-", "_")
-    for table in (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX):
+    for table in _TABLES:
         for n in sorted(table, key=len, reverse=True):
             if n in nm:
                 return table[n]

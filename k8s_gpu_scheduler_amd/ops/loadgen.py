@@ -1,7 +1,8 @@
 """Torch-facing wrappers for the HIP load kernels (native/hip/gemm.hip and its gemm_*.h kernel
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
 native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip,
-native/hip/sample.hip, native/hip/moe_route.hip, native/hip/moe_gemm.hip, native/hip/moe_combine.hip).
+native/hip/sample.hip, native/hip/moe_route.hip, native/hip/moe_gemm.hip, native/hip/moe_combine.hip,
+native/hip/rope_append_kv8.hip, native/hip/decode_attn_kv8.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
@@ -178,7 +179,23 @@ kernels) rely on:
     multiple of 16 bytes); scale rows any stride >= K / 32; C and bias as the other GEMMs'.  Tiles and fill rule are
     gemm_fp8's (models.workloads.default_gemm_mx_workgroups).  fp32 accumulation inside the scaled MFMA (one
     instruction per 128 k, its internal adder undocumented: tests/test_gpu_gemm_mx_exact.py measures it), K tiles
-    summed in order, one rounding to bf16; no split-K, no atomics, launches repeat bit for bit.
+    summed in order, one rounding to bf16; no split-K, no atomics, launches repeat bit for bit;
+  * THE FP8 KV FORMAT (rope_append with float8_e4m3fn caches and paged_decode_attention_kv8; stated once in
+    native/hip/api.h): k_cache [NB, Hkv, 32, 128] and v_cache [NB, Hkv, 128, 32] as for bf16, one OCP e4m3fn byte
+    per element, and k_scale, v_scale fp32 [Hkv], contiguous, on the operands' device; a stored byte c of KV head g
+    stands for e4m3fn(c) * scale[g].  Every other operand rule of the two ops is unchanged; both caches have one
+    dtype; paged_prefill_attention does not read such a cache.  THE QUANTISATION RULE for an fp32 value z: a NaN
+    gives 0x7F | sign << 7; otherwise the magnitude is rounded to the nearest e4m3fn value, ties to even (the
+    subnormal step is 2^-9 below 2^-6); whatever rounds above 448, +-Inf included, saturates to 0x7E; the sign bit
+    is always carried (-0.0 and a negative value that rounds to zero give 0x80).  torch's cast does not saturate
+    (500 -> NaN) and agrees only for |z| <= 448: quantize_kv8_reference is the reference.  rope_append stores
+    z = y / k_scale[g] for K, y the fp32 rotation result NOT first rounded to bf16, and z = float(v) / v_scale[g]
+    for V, both IEEE fp32 divisions; q_out is as for bf16 caches.  The decode kernels convert the bytes to bf16
+    in registers (exact for all 254 non-NaN codes; 0x7F and 0xFF are NaN) and keep the bf16 contract below with
+    scores = mfma_sum * (scale * k_scale[g]), the two scalars multiplied once in fp32, and
+    out = bf16((acc / lsum) * v_scale[g]); the split kernel's partials are unscaled by v_scale, the merge applies
+    it.  check=True also verifies that the scales are finite and > 0 (pinned by tests/test_gpu_rope_append_kv8_exact.py,
+    test_gpu_decode_kv8_exact.py and test_gpu_kv8_chain.py).
 
 Nothing outside the M x K, N x K and M x N windows (or the n floats of the triad) is read or
 written; the gather reads only the D elements of the rows the bags name (and the idx entries
@@ -570,14 +587,21 @@ ATTN_GROUPS = (1, 2, 4, 8, 16)          # query heads per KV head (the MFMA's 16
 
 def _paged_attn_operands(name: str, rows: str, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                          block_table: torch.Tensor, ctx_lens: torch.Tensor, out: Optional[torch.Tensor],
-                         q_start: Optional[torch.Tensor] = None):
+                         q_start: Optional[torch.Tensor] = None, kv8: bool = False):
     """The host checks the two paged attentions share: dtypes, ranks, the fixed head dim and block
     size, the head ratio, the cache layout, the table and ctx_lens against the S sequences, the output
     (made when None) and the strides and alignment of q and out.  `rows` names what q's first
     dimension counts: "sequence" (decode: S is that dimension) or "token" (prefill: S is
-    q_start's length less one).  Returns (S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table)."""
-    if q.dtype != torch.bfloat16 or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16:
-        raise TypeError(f"{name} expects bf16 q, k_cache and v_cache")
+    q_start's length less one).  kv8: both caches may be FP8 (float8_e4m3fn) instead of bf16.
+    Returns (S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table)."""
+    kinds = {k_cache.dtype, v_cache.dtype}
+    if kinds == {torch.bfloat16, FP8}:
+        raise TypeError(f"{name}: k_cache is {_OPERAND_NAMES[k_cache.dtype]} and v_cache {_OPERAND_NAMES[v_cache.dtype]}: "
+                        "one cache dtype, bf16 or float8_e4m3fn")
+    if kinds == {FP8} and not kv8:
+        raise TypeError(f"{name} expects bf16 q, k_cache and v_cache (it does not read an FP8 cache)")
+    if q.dtype != torch.bfloat16 or kinds not in ({torch.bfloat16}, {FP8}):
+        raise TypeError(f"{name} expects bf16 q, k_cache and v_cache" + (" (or float8_e4m3fn caches)" if kv8 else ""))
     if block_table.dtype != torch.int32 or ctx_lens.dtype != torch.int32:
         raise TypeError(f"{name} expects an int32 block_table and ctx_lens")
     if q_start is not None and q_start.dtype != torch.int32:
@@ -635,6 +659,31 @@ def _paged_attn_operands(name: str, rows: str, q: torch.Tensor, k_cache: torch.T
             _row_stride(block_table, S, max_blocks))
 
 
+def _kv8_scales(name: str, k_cache: torch.Tensor, k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
+                Hkv: int) -> bool:
+    """The scales of a paged cache against its dtype: True for FP8 caches (both scales needed: fp32 [Hkv],
+    contiguous, on the caches' device), False for bf16 ones (no scale may be given)."""
+    if k_cache.dtype != FP8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"{name}: k_scale / v_scale belong to float8_e4m3fn caches, these are bf16")
+        return False
+    if k_scale is None or v_scale is None:
+        raise ValueError(f"{name}: float8_e4m3fn caches need k_scale and v_scale")
+    for nm, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} expects an fp32 {nm}")
+        if t.device != k_cache.device:
+            raise ValueError(f"{name}: {nm} on {t.device}, the caches on {k_cache.device}")
+        if t.dim() != 1 or t.shape[0] != Hkv or not t.is_contiguous():
+            raise ValueError(f"{name}: {nm} {tuple(t.shape)} must be a contiguous [{Hkv}] vector, one scale per KV head")
+    return True
+
+
+def _scales_bad(k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    """A device boolean: a scale that is not finite and > 0 (a NaN compares false)."""
+    return ~((k_scale > 0) & k_scale.isfinite()).all() | ~((v_scale > 0) & v_scale.isfinite()).all()
+
+
 def _named_blocks_bad(block_table: torch.Tensor, ctx_lens: torch.Tensor, NB: int, max_blocks: int):
     """Two device booleans: a context length outside [0, 32 * max_blocks]; a block id outside [0, NB)
     among the ceil(ctx / 32) leading entries of a row, the only ones read as block ids."""
@@ -664,11 +713,40 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
     workspace is a contiguous, 16-byte aligned fp32 tensor on the operands' device of at least
     decode_split_workspace_floats(S, Hq, kv_splits) elements; None allocates one on the launch
     stream.  One workspace serves ONE launch in flight: two launches on different streams need two,
-    and a caller under graph capture passes its own (it must outlive the graph)."""
-    name = "paged_decode_attention"
-    _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, out)
+    and a caller under graph capture passes its own (it must outlive the graph).
+
+    The caches are bf16; paged_decode_attention_kv8 is the same attention over an FP8 cache."""
+    return _paged_decode("paged_decode_attention", False, q, k_cache, v_cache, block_table, ctx_lens, None, None, out,
+                         scale, stream, check, kv_splits, workspace)
+
+
+def paged_decode_attention_kv8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                               ctx_lens: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                               v_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                               scale: Optional[float] = None, stream: Optional[torch.cuda.Stream] = None,
+                               check: bool = True, kv_splits: int = 1,
+                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """paged_decode_attention over an FP8 cache: both caches torch.float8_e4m3fn (FP8) with k_scale and v_scale, fp32
+    [Hkv], contiguous, on the operands' device: a stored byte c of KV head g stands for e4m3fn(c) * scale[g] (THE
+    FP8 KV FORMAT, native/hip/api.h; rope_append writes it).  The kernels dequantise in registers -- exactly --
+    and keep the bf16 MFMAs: scores = mfma_sum * (scale * k_scale[g]), the two scalars multiplied once in fp32,
+    and out = bf16((acc / lsum) * v_scale[g]); everything else, kv_splits and the workspace included, is
+    paged_decode_attention's.  check=True also verifies, in the same sync, that the scales are finite and > 0.
+    bf16 caches (with or without scales) raise ValueError, mixed cache dtypes TypeError.  (A function of its
+    own and not two more keywords of paged_decode_attention: that function's parameter list is pinned.)"""
+    return _paged_decode("paged_decode_attention_kv8", True, q, k_cache, v_cache, block_table, ctx_lens, k_scale,
+                         v_scale, out, scale, stream, check, kv_splits, workspace)
+
+
+def _paged_decode(name, fp8, q, k_cache, v_cache, block_table, ctx_lens, k_scale, v_scale, out, scale, stream, check,
+                  kv_splits, workspace):
+    """The two decode wrappers: fp8 says which cache dtype the caller's function reads."""
+    _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, out, k_scale, v_scale)
     S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table = _paged_attn_operands(
-        name, "sequence", q, k_cache, v_cache, block_table, ctx_lens, out)
+        name, "sequence", q, k_cache, v_cache, block_table, ctx_lens, out, kv8=fp8)
+    kv8 = _kv8_scales(name, k_cache, k_scale, v_scale, Hkv)
+    if fp8 and not kv8:
+        raise ValueError(f"{name} reads float8_e4m3fn caches, these are bf16: paged_decode_attention reads them")
     if isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or not 1 <= kv_splits <= ATTN_MAX_KV_SPLITS:
         raise ValueError(f"{name}: kv_splits = {kv_splits!r} must be an int in [1, {ATTN_MAX_KV_SPLITS}]")
     if kv_splits > 1 and workspace is not None:
@@ -690,11 +768,19 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
         sp = _stream_ptr(stream, q.device)
         if check:
             with _launch_stream(stream, q.device):
-                bad = torch.stack(_named_blocks_bad(block_table, ctx_lens, NB, max_blocks)).tolist()    # the one sync
+                bad = torch.stack(_named_blocks_bad(block_table, ctx_lens, NB, max_blocks)
+                                  + ((_scales_bad(k_scale, v_scale),) if kv8 else ())).tolist()         # the one sync
             if bad[0]:
                 raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
             if bad[1]:
                 raise ValueError(f"{name}: a block id is outside [0, {NB})")
+            if kv8 and bad[2]:
+                raise ValueError(f"{name}: k_scale and v_scale must be finite and > 0")
+        if kv8 and kv_splits == 1:
+            h.paged_decode_kv8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                               v_scale.data_ptr(), block_table.data_ptr(), ctx_lens.data_ptr(), out.data_ptr(), S, Hq,
+                               Hkv, ld_q, ld_out, ld_table, float(scale), sp)
+            return out
         if kv_splits == 1:
             h.paged_decode_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
                                 ctx_lens.data_ptr(), out.data_ptr(), S, Hq, Hkv, ld_q, ld_out, ld_table, float(scale),
@@ -705,6 +791,12 @@ def paged_decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
             with _launch_stream(stream, q.device):
                 workspace = torch.empty(decode_split_workspace_floats(S, Hq, kv_splits), dtype=torch.float32,
                                         device=q.device)
+        if kv8:
+            h.paged_decode_split_kv8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                                     v_scale.data_ptr(), block_table.data_ptr(), ctx_lens.data_ptr(),
+                                     workspace.data_ptr(), out.data_ptr(), S, Hq, Hkv, kv_splits, ld_q, ld_out, ld_table,
+                                     float(scale), sp)
+            return out
         h.paged_decode_split_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
                                   ctx_lens.data_ptr(), workspace.data_ptr(), out.data_ptr(), S, Hq, Hkv, kv_splits,
                                   ld_q, ld_out, ld_table, float(scale), sp)
@@ -794,7 +886,8 @@ def _storage_range(t: torch.Tensor):
 def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                 block_table: torch.Tensor, ctx_lens: torch.Tensor, q_start: torch.Tensor,
                 max_q_len: Optional[int] = None, q_out: Optional[torch.Tensor] = None,
-                stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
+                stream: Optional[torch.cuda.Stream] = None, check: bool = True,
+                k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Rotary position embedding of q and K and the append of the new K / V to the paged KV cache of the
     attentions.  qkv is [Tq, Hq + 2 * Hkv, 128] -- the Hq query heads, the Hkv K heads, the Hkv V heads,
     what a fused QKV projection produces --, packed over the S sequences by q_start (int32 [S + 1], CSR)
@@ -812,9 +905,16 @@ def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
     when None), the table entries the chunks touch -- (ctx - q_len) // 32 .. (ctx - 1) // 32 of each
     sequence with q_len > 0 -- within [0, NB) and pairwise distinct over the launch (two sequences
     appending into one block is a silent race).  check=False needs max_q_len and never syncs: for
-    callers that guarantee all of it, and under graph capture."""
+    callers that guarantee all of it, and under graph capture.
+
+    The caches are bf16, or both torch.float8_e4m3fn (FP8) with k_scale and v_scale, fp32 [Hkv], contiguous, on
+    the operands' device (THE FP8 KV FORMAT, native/hip/api.h).  q_out is then unchanged; the K byte is
+    quantize_kv8_reference(y / k_scale[g]) with y the fp32 rotation result, NOT first rounded to bf16, and the V
+    byte quantize_kv8_reference(float(v) / v_scale[g]), both divisions IEEE fp32 (rope_append_kv8_reference).
+    check=True also verifies, in the same sync, that the scales are finite and > 0.  bf16 caches with a scale
+    given raise ValueError, mixed cache dtypes TypeError."""
     name = "rope_append"
-    _check_devices(name, qkv, cos_sin, k_cache, v_cache, block_table, ctx_lens, q_start, q_out)
+    _check_devices(name, qkv, cos_sin, k_cache, v_cache, block_table, ctx_lens, q_start, q_out, k_scale, v_scale)
     if cos_sin.dtype != torch.float32:
         raise TypeError(f"{name} expects an fp32 cos_sin")
     if qkv.dtype != torch.bfloat16:
@@ -838,7 +938,8 @@ def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
     # the q heads as a view: the attentions' checks then cover the caches, the table, ctx_lens, q_start, the
     # head dim, the group, qkv's alignment and q_out
     S, Hq, Hkv, NB, max_blocks, q_out, _, ld_q_out, ld_table = _paged_attn_operands(
-        name, "token", qkv[:, :Hq], k_cache, v_cache, block_table, ctx_lens, q_out, q_start)
+        name, "token", qkv[:, :Hq], k_cache, v_cache, block_table, ctx_lens, q_out, q_start, kv8=True)
+    kv8 = _kv8_scales(name, k_cache, k_scale, v_scale, Hkv)
     if cos_sin.shape[1] != ATTN_HEAD_DIM:
         raise ValueError(f"{name}: cos_sin must be [max_pos, {ATTN_HEAD_DIM}]: 64 cosines, then 64 sines")
     if not cos_sin.is_contiguous() or cos_sin.data_ptr() % 16:
@@ -873,7 +974,8 @@ def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
                                    ((q_len < 0).any() | (q_start[0] < 0) | (q_start[-1] > Tq)).long(),
                                    (q_len > ctx_lens).any().long(), q_len.max().long(),
                                    (((block_table < 0) | (block_table >= NB)) & touched).any().long(),
-                                   (ids[1:] == ids[:-1]).any().long()]).tolist()                # the one sync
+                                   (ids[1:] == ids[:-1]).any().long()]
+                                  + ([_scales_bad(k_scale, v_scale).long()] if kv8 else [])).tolist()   # the one sync
             if bad[0]:
                 raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
             if bad[1]:
@@ -890,7 +992,14 @@ def rope_append(qkv: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
                 raise ValueError(f"{name}: a block id is outside [0, {NB})")
             if bad[6]:
                 raise ValueError(f"{name}: two chunks append into one cache block")
-        if max_q_len:
+            if kv8 and bad[7]:
+                raise ValueError(f"{name}: k_scale and v_scale must be finite and > 0")
+        if max_q_len and kv8:
+            h.rope_append_kv8(qkv.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                              k_scale.data_ptr(), v_scale.data_ptr(), block_table.data_ptr(), ctx_lens.data_ptr(),
+                              q_start.data_ptr(), q_out.data_ptr(), S, Hq, Hkv, int(max_q_len), int(max_pos), ld_qkv,
+                              ld_q_out, ld_table, sp)
+        elif max_q_len:
             h.rope_append_bf16(qkv.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                block_table.data_ptr(), ctx_lens.data_ptr(), q_start.data_ptr(), q_out.data_ptr(), S, Hq,
                                Hkv, int(max_q_len), int(max_pos), ld_qkv, ld_q_out, ld_table, sp)
@@ -1569,6 +1678,71 @@ def gemm_mx(a_q: torch.Tensor, a_scales: torch.Tensor, w_q: torch.Tensor, w_scal
                      M, N, K, lda, ld_as, ldw, ld_ws, out.stride(0), _mx_code(a_fmt), bool(relu),
                      _stream_ptr(stream, a_q.device), cu_budget)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ FP8 KV cache
+def quantize_kv8_reference(z: torch.Tensor) -> torch.Tensor:
+    """THE quantisation rule of the FP8 KV cache (native/hip/api.h) on the CPU, in integer torch ops on the fp32
+    bits: z fp32, any shape -> uint8 e4m3fn codes of the same shape, bit for bit what rope_append stores for
+    z = value / scale.  A NaN gives 0x7F | sign << 7; otherwise the magnitude is rounded to the nearest e4m3fn value,
+    ties to even (step 2^-9 below 2^-6), whatever rounds above 448, +-Inf included, saturates to 0x7E; the sign bit
+    is always carried (-0.0 and a negative value that rounds to zero give 0x80).  With mag the 31 magnitude bits and
+    e = mag >> 23: for e >= 121 (|z| >= 2^-6) the code is RNE(mag / 2^20) - (120 << 3) -- the rounding carry walks
+    into the exponent by itself --, below that RNE(significand / 2^(141 - e)) in units of 2^-9."""
+    if z.dtype != torch.float32 or z.is_cuda:
+        raise ValueError("quantize_kv8_reference expects a CPU fp32 tensor")
+    bits = z.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    sign, mag = bits >> 31, bits & 0x7FFFFFFF
+    e = mag >> 23
+
+    def rne(x, s):                                                         # round(x / 2^s) to nearest even, s >= 1
+        return (x + (torch.ones_like(s) << (s - 1)) - 1 + ((x >> s) & 1)) >> s
+    normal = rne(mag, torch.full_like(mag, 20)) - (120 << 3)
+    sig = (mag & 0x7FFFFF) | ((e > 0).to(torch.int64) << 23)              # |z| = sig * 2^(max(e, 1) - 150)
+    sub = rne(sig, (141 - e.clamp(min=1)).clamp(min=1, max=40))           # below 2^-10: 0
+    code = torch.where(e >= 121, normal, sub).clamp(max=0x7E)
+    code = torch.where(mag > 0x7F800000, torch.full_like(code, 0x7F), code)
+    return (code | (sign << 7)).to(torch.uint8)
+
+
+def dequantize_kv8_reference(codes: torch.Tensor, scale) -> torch.Tensor:
+    """The values the bytes of an FP8 KV cache stand for, float64 on the CPU: e4m3fn(c) * scale, both exact in
+    float64 (0x7F and 0xFF are NaN).  codes: uint8 or float8_e4m3fn, any shape; scale: a float, or a tensor that
+    broadcasts against codes (one scale per KV head: scale.view(1, Hkv, 1, 1) for a cache)."""
+    if codes.is_cuda or codes.dtype not in (FP8, torch.uint8):
+        raise ValueError("dequantize_kv8_reference expects CPU float8_e4m3fn codes (or their bytes as uint8)")
+    el = (codes.view(FP8) if codes.dtype == torch.uint8 else codes).to(torch.float32).to(torch.float64)
+    return el * (scale.to(torch.float64) if isinstance(scale, torch.Tensor) else float(scale))
+
+
+def rope_append_kv8_reference(qkv: torch.Tensor, cos_sin: torch.Tensor, ctx_lens: torch.Tensor, q_start: torch.Tensor,
+                              k_scale: torch.Tensor, v_scale: torch.Tensor):
+    """(k_codes, v_codes) uint8 [Tq, Hkv, 128]: the cache bytes rope_append writes for every row of qkv (bf16
+    [Tq, Hq + 2 Hkv, 128], CPU) that belongs to a chunk -- zeros elsewhere.  The rotation is computed in float64
+    (y[i] = x1 c - x2 s, y[i + 64] = x2 c + x1 s at the row's position ctx - q_len + i) and cast to fp32 once,
+    then z = y / k_scale[g] and z = float(v) / v_scale[g] are fp32 divisions and quantize_kv8_reference gives the
+    bytes.  Where the float64 rotation is exact in fp32 (the exact regimes of the tests) that is bit for bit the
+    kernel's result; otherwise the kernel's fp32 FMA may land one ulp away, and a near-tie one e4m3 step."""
+    Hkv = k_scale.numel()
+    Tq, Ht, D = qkv.shape
+    Hq, half = Ht - 2 * Hkv, ATTN_HEAD_DIM // 2
+    k64 = torch.zeros(Tq, Hkv, D, dtype=torch.float64)
+    live = torch.zeros(Tq, dtype=torch.bool)
+    starts = q_start.tolist()
+    for s, ctx in enumerate(ctx_lens.tolist()):
+        r0, r1 = starts[s], starts[s + 1]
+        if r1 <= r0:
+            continue
+        cs = cos_sin[ctx - (r1 - r0) + torch.arange(r1 - r0)].double()[:, None, :]
+        x = qkv[r0:r1, Hq:Hq + Hkv].double()
+        x1, x2, c, sn = x[..., :half], x[..., half:], cs[..., :half], cs[..., half:]
+        k64[r0:r1] = torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn], dim=-1)
+        live[r0:r1] = True
+    kz = k64.float() / k_scale.float().view(1, Hkv, 1)
+    vz = qkv[:, Hq + Hkv:].float() / v_scale.float().view(1, Hkv, 1)
+    keep = live.view(Tq, 1, 1)
+    return (torch.where(keep, quantize_kv8_reference(kz), torch.zeros((), dtype=torch.uint8)),
+            torch.where(keep, quantize_kv8_reference(vz), torch.zeros((), dtype=torch.uint8)))
 
 
 def gemm_flops(M: int, N: int, K: int) -> float:

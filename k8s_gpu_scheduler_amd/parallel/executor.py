@@ -126,7 +126,7 @@ def _prefill_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
     return _paged_operands(o, o.M * o.q, g, device) + (q_start,)
 
 
-def _rope_append_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+def _rope_append_operands(o: Op, g: torch.Generator, device: torch.device, cache_dtype=torch.bfloat16) -> tuple:
     """(q_out, qkv, cos_sin, k_cache, v_cache, table, ctx, q_start): the last o.q of every sequence's K
     context tokens are its chunk, packed in sequence order; qkv is randn, the caches (M * K / 32 blocks
     that a seeded random permutation deals out) are what the op writes and start as zeros."""
@@ -139,13 +139,59 @@ def _rope_append_operands(o: Op, g: torch.Generator, device: torch.device) -> tu
     nb = o.M * per_seq
     qkv = torch.randn(o.M * o.q, o.N + 2 * o.rows, D, generator=g).to(torch.bfloat16).to(device)
     cos_sin = loadgen.rope_table(o.K).to(device)
-    kc = torch.zeros(nb, o.rows, T, D, dtype=torch.bfloat16, device=device)
-    vc = torch.zeros(nb, o.rows, D, T, dtype=torch.bfloat16, device=device)
+    kc = torch.zeros(nb, o.rows, T, D, dtype=cache_dtype, device=device)
+    vc = torch.zeros(nb, o.rows, D, T, dtype=cache_dtype, device=device)
     table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
     ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
     q_start = (torch.arange(o.M + 1, dtype=torch.int32) * o.q).to(device)
     q_out = torch.empty(o.M * o.q, o.N, D, dtype=torch.bfloat16, device=device)
     return q_out, qkv, cos_sin, kc, vc, table, ctx, q_start
+
+
+KV8_K_SCALE, KV8_V_SCALE = 0.5, 0.25          # the kv8 ops' scales, the same for every KV head
+
+
+def _kv8_scales(o: Op, device: torch.device) -> tuple:
+    return (torch.full((o.rows,), KV8_K_SCALE, dtype=torch.float32, device=device),
+            torch.full((o.rows,), KV8_V_SCALE, dtype=torch.float32, device=device))
+
+
+def _paged_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """_paged_operands for decode over an FP8 cache, and (k_scale, v_scale): the caches repeat one seeded pattern
+    of finite e4m3fn codes of magnitude <= 2 (the low seven bits drawn from [0, 0x41): 0x40 is 2.0), any sign."""
+    T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
+    if o.K % T:
+        raise ValueError(f"attention context {o.K} is no multiple of {T}")
+    per_seq = o.K // T
+    nb = o.M * per_seq
+    n = min(nb, ATTN_PATTERN_BLOCKS)
+    q = torch.randn(o.M, o.N, D, generator=g).to(torch.bfloat16).to(device)
+
+    def cache(*shape: int) -> torch.Tensor:
+        pat = torch.randint(0, 0x41, (n,) + shape, generator=g) | (torch.randint(0, 2, (n,) + shape, generator=g) << 7)
+        return _repeat(pat.to(torch.uint8).to(device), nb).view(loadgen.FP8)
+    kc, vc = cache(o.rows, T, D), cache(o.rows, D, T)
+    table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
+    ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
+    out = torch.empty(o.M, o.N, D, dtype=torch.bfloat16, device=device)
+    return (out, q, kc, vc, table, ctx) + _kv8_scales(o, device)
+
+
+def _attn_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, q, k_cache, v_cache, table, ctx, k_scale, v_scale)."""
+    return _paged_kv8_operands(o, g, device)
+
+
+def _attn_split_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, q, k_cache, v_cache, table, ctx, ws, k_scale, v_scale): the workspace as _attn_split_operands makes it."""
+    ws = torch.empty(loadgen.decode_split_workspace_floats(o.M, o.N, o.splits), dtype=torch.float32, device=device)
+    t = _paged_kv8_operands(o, g, device)
+    return t[:6] + (ws,) + t[6:]
+
+
+def _rope_append_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """_rope_append_operands with FP8 caches that start as zeros (code 0x00), and (k_scale, v_scale)."""
+    return _rope_append_operands(o, g, device, loadgen.FP8) + _kv8_scales(o, device)
 
 
 def _add_rmsnorm_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
@@ -302,6 +348,23 @@ def _launch_rope_append(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     loadgen.rope_append(qkv, cos_sin, kc, vc, table, ctx, q_start, max_q_len=o.q, q_out=q_out, stream=st, check=False)
 
 
+def _launch_attn_kv8(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, q, kc, vc, table, ctx, ks, vs = t
+    loadgen.paged_decode_attention_kv8(q, kc, vc, table, ctx, ks, vs, out=out, stream=st, check=False)
+
+
+def _launch_attn_split_kv8(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, q, kc, vc, table, ctx, ws, ks, vs = t
+    loadgen.paged_decode_attention_kv8(q, kc, vc, table, ctx, ks, vs, out=out, stream=st, check=False,
+                                       kv_splits=o.splits, workspace=ws)
+
+
+def _launch_rope_append_kv8(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    q_out, qkv, cos_sin, kc, vc, table, ctx, q_start, ks, vs = t
+    loadgen.rope_append(qkv, cos_sin, kc, vc, table, ctx, q_start, max_q_len=o.q, q_out=q_out, stream=st, check=False,
+                        k_scale=ks, v_scale=vs)
+
+
 def _launch_add_rmsnorm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     y, res_out, x, residual, weight = t
     loadgen.add_rmsnorm(x, weight, residual, out=y, residual_out=res_out, stream=st)
@@ -357,7 +420,8 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # q_start); add_rmsnorm (y, res_out, x, residual, weight); swiglu (out, gate_up); sample (out, logits, u,
 # temperature, top_k, top_p); moe_route (topk_ids, logits, topk_w, sorted_ids, tile_expert, expert_offsets,
 # slot_pos); moe_gemm (out, a, w, sorted_ids, tile_expert); moe_combine (out, y, slot_pos, topk_w); quant_mx (q, scales,
-# x); gemm_mx (c, a_q, a_scales, w_q, w_scales, bias); triad (x, y, z), x = y + s z.
+# x); gemm_mx (c, a_q, a_scales, w_q, w_scales, bias); attn_kv8, attn_split_kv8 and rope_append_kv8 their bf16 kinds'
+# and (k_scale, v_scale), the caches float8_e4m3fn; triad (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -374,6 +438,9 @@ OP_KINDS = {
     "moe_combine": (_moe_combine_operands, _launch_moe_combine, 0),
     "quant_mx": (_quant_mx_operands, _launch_quant_mx, 0),
     "gemm_mx": (_gemm_mx_operands, _launch_gemm_mx, 0),
+    "attn_kv8": (_attn_kv8_operands, _launch_attn_kv8, 0),
+    "attn_split_kv8": (_attn_split_kv8_operands, _launch_attn_split_kv8, 0),
+    "rope_append_kv8": (_rope_append_kv8_operands, _launch_rope_append_kv8, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

@@ -157,6 +157,30 @@ void gemm_mx_nt(uintptr_t a, uintptr_t a_scales, uintptr_t w, uintptr_t w_scales
 int gemm_mx_workgroups(int M, int N, int K, int cu_budget);
 // the fill rule of gemm_fp8_nt and gemm_mx_nt (gemm.hip): 128 x 128 tiles, else 64 x 64
 bool fp8_tile_128(int M, int N, int cu_budget);
+// FP8 paged-KV cache -- native/hip/rope_append_kv8.hip, decode_attn_kv8.hip.  THE FP8 KV FORMAT: k_cache uint8
+// [NB, Hkv, 32, 128] and v_cache uint8 [NB, Hkv, 128, 32], the logical layout of the bf16 caches with one OCP e4m3fn
+// byte per element; k_scale and v_scale fp32 [Hkv] (4-byte aligned).  A stored byte c of KV head g stands for
+// e4m3fn(c) * scale[g].  THE QUANTISATION RULE for an fp32 value z (the writer computes z = value / scale[g], an IEEE
+// fp32 division): a NaN gives 0x7F | sign << 7; otherwise |z| is rounded to the nearest e4m3fn magnitude, ties to even
+// (the subnormal step is 2^-9 below 2^-6), anything that rounds above 448, +-Inf included, saturates to 0x7E (448);
+// z's sign bit is always carried (-0.0, and a negative value that rounds to zero, give 0x80).  e4m3fn -> bf16 is exact
+// for all 254 non-NaN codes, so the readers dequantise in registers and keep the bf16 MFMAs.
+// rope_append_bf16 into such a cache: q_out as there; K is quantised from the fp32 rotation result (not first rounded
+// to bf16) divided by k_scale[g], V from float(v) / v_scale[g]
+void rope_append_kv8(uintptr_t qkv, uintptr_t cos_sin, uintptr_t k_cache, uintptr_t v_cache, uintptr_t k_scale,
+                     uintptr_t v_scale, uintptr_t block_table, uintptr_t ctx_lens, uintptr_t q_start, uintptr_t q_out,
+                     int S, int Hq, int Hkv, int max_q_len, int max_pos, int64_t ld_qkv, int64_t ld_q_out,
+                     int64_t ld_table, uintptr_t stream);
+// paged_decode_bf16 / paged_decode_split_bf16 over such a cache: scores = mfma_sum * (scale * k_scale[g]), the two
+// scalars multiplied once in fp32; out = bf16((acc / lsum) * v_scale[g]).  The split kernel's partials are unscaled by
+// v_scale (the merge applies it); workgroups, workspace rows and the partition rule are the bf16 functions'
+void paged_decode_kv8(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t k_scale, uintptr_t v_scale,
+                      uintptr_t block_table, uintptr_t ctx_lens, uintptr_t out, int S, int Hq, int Hkv, int64_t ld_q,
+                      int64_t ld_out, int64_t ld_table, float scale, uintptr_t stream);
+void paged_decode_split_kv8(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t k_scale, uintptr_t v_scale,
+                            uintptr_t block_table, uintptr_t ctx_lens, uintptr_t workspace, uintptr_t out, int S,
+                            int Hq, int Hkv, int kv_splits, int64_t ld_q, int64_t ld_out, int64_t ld_table,
+                            float scale, uintptr_t stream);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

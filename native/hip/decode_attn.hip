@@ -68,17 +68,6 @@
 namespace gs {
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kOLd = kHeadDim + 4;                // fp32 row of the LDS image: 528 bytes, 16-byte aligned
-constexpr int kPartLd = kOLd;                     // a split's workspace row: 128 accumulators, m, l, 2 words unused
-constexpr int kMaxKvSplits = 32;
-
-struct Partials {
-  float o[kWaves][kMaxGroup][kOLd];
-  float m[kWaves][kMaxGroup];
-  float l[kWaves][kMaxGroup];
-};
-
 // The walk of one workgroup over the blocks [blk_lo, blk_hi) of sequence s (ctx tokens) for KV head
 // kvh: the whole sequence for paged_decode_kernel, one split's range for paged_decode_split_kernel.
 // Leaves each wave's partial (O, m, l) in sm, behind a barrier.  Only block ceil(ctx / 32) - 1 can
@@ -198,52 +187,8 @@ __device__ __forceinline__ void walk_blocks(Partials& sm, const __bf16* __restri
     l += __shfl_xor(l, 32, kWave);
   }
 
-  // the wave's partial: O^T register r of db is d = 16 db + 4 g + r of head col
-#pragma unroll
-  for (int db = 0; db < 8; ++db) *reinterpret_cast<f32x4*>(&sm.o[wave][col][16 * db + 4 * g]) = o[db];
-  if (g == 0) {
-    sm.m[wave][col] = m;
-    sm.l[wave][col] = l;
-  }
+  store_partial(sm, wave, col, g, o, m, l);
   __syncthreads();
-}
-
-// The merge of the four waves' partials for head c of the group, elements d0 .. d0 + 7: each is
-// weighed by a_w = exp(m_w - max m).  acc = sum_w a_w O_w, mx = max_w m_w, lsum = sum_w a_w l_w
-__device__ __forceinline__ void merge_waves(const Partials& sm, int c, int d0, float (&acc)[8], float& mx,
-                                            float& lsum) {
-  const float ninf = -__builtin_inff();
-  float mw[kWaves];
-  mx = ninf;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    mw[w] = sm.m[w][c];
-    mx = fmaxf(mx, mw[w]);
-  }
-  lsum = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    // a wave without blocks (all of them when ctx == 0) has m = -inf: weight 0, never (-inf) - (-inf)
-    const float a = mw[w] == ninf ? 0.f : __builtin_amdgcn_exp2f((mw[w] - mx) * kLog2e);
-    lsum += a * sm.l[w][c];
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(&sm.o[w][c][d0]);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(&sm.o[w][c][d0 + 4]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      acc[e] += a * lo[e];
-      acc[4 + e] += a * hi[e];
-    }
-  }
-}
-
-// lsum == 0 only for ctx == 0 (every weight 0): +0.0.  A NaN normaliser divides: NaN out
-__device__ __forceinline__ bf16x8 normalised(const float (&acc)[8], float lsum) {
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (__bf16)(lsum == 0.f ? 0.f : acc[e] / lsum);
-  return r;
 }
 
 __global__ void __launch_bounds__(256, 4) paged_decode_kernel(const __bf16* __restrict__ q,
@@ -293,12 +238,7 @@ __global__ void __launch_bounds__(256, 4) paged_decode_split_kernel(
     float acc[8], mx, lsum;
     merge_waves(sm, c, d0, acc, mx, lsum);           // an empty split: zeros, m = -inf, l = 0
     float* row = workspace + (((size_t)s * Hq + kvh * group + c) * kv_splits + p) * kPartLd;
-    *reinterpret_cast<f32x4*>(row + d0) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-    *reinterpret_cast<f32x4*>(row + d0 + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
-    if (d0 == 0) {
-      row[kHeadDim] = mx;
-      row[kHeadDim + 1] = lsum;
-    }
+    store_split_row(row, d0, acc, mx, lsum);
   }
 }
 
