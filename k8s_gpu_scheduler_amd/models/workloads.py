@@ -68,6 +68,9 @@ attentions over an FP8 (OCP e4m3fn) paged cache with one fp32 scale per KV head 
 paged_decode_attention_kv8) -- the attentions stream HALF the cache bytes of "attn" / "attn_split"
 for the same flops, at the cost of a byte -> bf16 conversion in front of every MFMA operand, and hold twice the
 sequences per GiB; the append rounds every K and V element with an IEEE division and a few integer operations.
+A nineteenth is "prefill_kv8" (LLM_KV8_PREFILL), chunked-prefill attention over that FP8 cache
+(ops.loadgen.paged_prefill_attention_kv8): "prefill"'s MFMA work behind a byte -> bf16 conversion of every K and V
+fragment, over half the cache bytes -- the conversion sits beside the MFMAs that bound the kernel, not behind HBM.
 """
 from __future__ import annotations
 
@@ -114,6 +117,7 @@ class Op:
     #                        | "moe_combine" (bf16 weighted sum of each token's K expert output rows of N elements)
     #                        | "rope_append_kv8", "attn_kv8", "attn_split_kv8" ("rope_append", "attn", "attn_split" over an FP8
     #                          e4m3fn cache with one fp32 scale per KV head; the fields of their bf16 kinds)
+    #                        | "prefill_kv8" ("prefill" over such a cache; the fields of "prefill")
     #                        | "quant_mx" (bf16 -> MX blocks of format `fmt`: M rows of N elements)
     #                        | "gemm_mx" (MX GEMM, bf16 out: activations of format `fmt` on fp4 weights)
     M: int = 0             # gather: bags; attn, attn_split, prefill, rope_append: sequences; add_rmsnorm, swiglu, sample: rows;
@@ -143,7 +147,7 @@ class Op:
     @property
     def on_mfma(self) -> bool:
         """MFMA work in the roofline: costed max(flops term, bytes term), its flops on the MFMA side."""
-        return self.is_gemm or self.kind in ("prefill", "moe_gemm", "gemm_mx")
+        return self.is_gemm or self.kind in ("prefill", "prefill_kv8", "moe_gemm", "gemm_mx")
 
     @property
     def flops(self) -> float:
@@ -151,7 +155,7 @@ class Op:
             return 1.0 * self.M * self.K * self.N                 # one add per gathered element
         if self.kind in ("attn", "attn_split", "attn_kv8", "attn_split_kv8"):      # q . K^T and P . V, a multiply-add each
             return 4.0 * self.M * self.N * self.K * ATTN_HEAD_DIM
-        if self.kind == "prefill":                                # the same per (query, token at or below it) pair:
+        if self.kind in ("prefill", "prefill_kv8"):               # the same per (query, token at or below it) pair:
             pairs = self.q * (self.K - self.q) + self.q * (self.q + 1) / 2        # the prefix, then the causal triangle
             return 4.0 * ATTN_HEAD_DIM * self.M * self.N * pairs
         if self.kind in ("rope_append", "rope_append_kv8"):       # two multiplies and one add per rotated element of q and K
@@ -189,9 +193,12 @@ class Op:
             if self.kind.startswith("attn_split"):                # the fp32 workspace, written and read once
                 b += 2 * 4.0 * decode_split_workspace_floats(self.M, self.N, self.splits)
             return b
-        if self.kind == "prefill":                                # K and V read once, q and out, table, ctx_lens, q_start
-            return (4.0 * self.M * self.rows * self.K * ATTN_HEAD_DIM + 4.0 * self.M * self.q * self.N * ATTN_HEAD_DIM
-                    + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + 4.0 * (self.M + 1))
+        if self.kind in ("prefill", "prefill_kv8"):               # K and V read once, q and out, table, ctx_lens, q_start
+            kv8 = self.kind == "prefill_kv8"                      # 1-byte K / V elements and the two [Hkv] fp32 scale vectors
+            return ((2.0 if kv8 else 4.0) * self.M * self.rows * self.K * ATTN_HEAD_DIM
+                    + 4.0 * self.M * self.q * self.N * ATTN_HEAD_DIM
+                    + 4.0 * self.M * self.K / ATTN_BLOCK_TOKENS + 4.0 * self.M + 4.0 * (self.M + 1)
+                    + (8.0 * self.rows if kv8 else 0.0))
         if self.kind in ("rope_append", "rope_append_kv8"):
             kv8 = self.kind == "rope_append_kv8"                  # 1-byte K / V elements and the two [Hkv] fp32 scale vectors
             tokens = self.M * self.q
@@ -243,7 +250,7 @@ class Op:
             return default_gather_workgroups(self.M)
         if self.kind in ("attn", "attn_kv8"):
             return default_attn_workgroups(self.M, self.rows)
-        if self.kind == "prefill":
+        if self.kind in ("prefill", "prefill_kv8"):
             return default_prefill_workgroups(self.M, self.N, self.rows, self.q)
         if self.kind in ("attn_split", "attn_split_kv8"):
             return default_attn_split_workgroups(self.M, self.rows, self.splits)
@@ -559,12 +566,37 @@ LLM_KV8: Dict[str, Workload] = {
                                        Op("gemm", 64, 4096, 4096)), 1.25),
 }
 
-_TABLES = (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX, LLM_KV8)
+
+# Workloads of the "prefill_kv8" kind, which those pinned tables do not list either (a table of its own: LLM_KV8 is
+# pinned to its two entries): the prefill side of a stack that keeps its KV cache in FP8.  Each op keeps its own
+# operands, as everywhere in the executor: the append writes one cache and the attention reads another.
+#   llm_kv8_layer_prefill_2048  llm_layer_prefill_2048 with the two kv8 kinds: two sequences that each append a
+#                               1,024-token chunk to 3,072 cached tokens.  Each op's K + V are 16 MiB and stay in the
+#                               Infinity Cache: the compute-bound case, where the conversion cost shows undiluted.
+#                               The executor allocates 0.252 GiB (0.22 of it the GEMMs' and qkv's), declared 0.5
+#   llm_kv8_chunk_prefill_64    continuous batching / long-prefix chunks: 64 sequences that each append a 32-token
+#                               chunk to 8,160 cached tokens.  128 columns per (sequence, KV head): one workgroup
+#                               each, 512 workgroups.  Each op's K + V are 1 GiB (bf16: 2 GiB) and stream from HBM;
+#                               about 256 flops per cache byte (bf16: 128), near the machine balance.  The executor
+#                               allocates 2.22 GiB, declared 2.25
+# The FP8 prefill is the nineteenth kernel character; no co-run groups are measured with it yet
+LLM_KV8_PREFILL: Dict[str, Workload] = {
+    "llm_kv8_layer_prefill_2048": Workload("llm_kv8_layer_prefill_2048", "llm_kv8_layer_prefill", "hip", 2048,
+                                           (Op("gemm", 2048, 6144, 4096), Op("rope_append_kv8", 2, 32, 4096, rows=8, q=1024),
+                                            Op("prefill_kv8", 2, 32, 4096, rows=8, q=1024), Op("gemm", 2048, 4096, 4096)),
+                                           0.5),
+    "llm_kv8_chunk_prefill_64": Workload("llm_kv8_chunk_prefill_64", "llm_kv8_chunk_prefill", "hip", 64,
+                                         (Op("gemm", 2048, 6144, 4096), Op("rope_append_kv8", 64, 32, 8192, rows=8, q=32),
+                                          Op("prefill_kv8", 64, 32, 8192, rows=8, q=32), Op("gemm", 2048, 4096, 4096)),
+                                         2.25),
+}
+
+_TABLES = (CATALOG, EXTRA, STAGED, LONG_CONTEXT, LLM_LAYER, LLM_BLOCK, LLM_HEAD, LLM_MOE, LLM_MX, LLM_KV8, LLM_KV8_PREFILL)
 
 
 def get(name: str) -> Workload:
-    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head, LLM-MoE, LLM-MX or LLM-KV8 workload by
-    exact name."""
+    """A catalog, extra, staged, long-context, LLM-layer, LLM-block, LLM-head, LLM-MoE, LLM-MX, LLM-KV8 or
+    LLM-KV8-prefill workload by exact name."""
     for table in _TABLES:
         w = table.get(name)
         if w is not None:
@@ -576,7 +608,7 @@ def workload_for_pod(pod_name: str) -> Workload:
     """Same matching rule as the recommender: first catalog name that is a substring of
     the pod name with '-' -> '_' (reference recom_server.py:67-71); the extra workloads after
     the catalog, the staged ones after those, then the long-context ones, the LLM-layer ones, the LLM-block
-    ones, the LLM-head ones, the LLM-MoE ones, the LLM-MX ones, the LLM-KV8 ones last."""
+    ones, the LLM-head ones, the LLM-MoE ones, the LLM-MX ones, the LLM-KV8 ones, the LLM-KV8-prefill ones last."""
     nm = pod_name.replace("-", "_")
     for table in _TABLES:
         for n in sorted(table, key=len, reverse=True):

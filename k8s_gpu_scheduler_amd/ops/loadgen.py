@@ -2,7 +2,7 @@
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
 native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip,
 native/hip/sample.hip, native/hip/moe_route.hip, native/hip/moe_gemm.hip, native/hip/moe_combine.hip,
-native/hip/rope_append_kv8.hip, native/hip/decode_attn_kv8.hip).
+native/hip/rope_append_kv8.hip, native/hip/decode_attn_kv8.hip, native/hip/prefill_attn_kv8.hip).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;
@@ -180,11 +180,12 @@ kernels) rely on:
     gemm_fp8's (models.workloads.default_gemm_mx_workgroups).  fp32 accumulation inside the scaled MFMA (one
     instruction per 128 k, its internal adder undocumented: tests/test_gpu_gemm_mx_exact.py measures it), K tiles
     summed in order, one rounding to bf16; no split-K, no atomics, launches repeat bit for bit;
-  * THE FP8 KV FORMAT (rope_append with float8_e4m3fn caches and paged_decode_attention_kv8; stated once in
+  * THE FP8 KV FORMAT (rope_append with float8_e4m3fn caches, paged_decode_attention_kv8 and
+    paged_prefill_attention_kv8; stated once in
     native/hip/api.h): k_cache [NB, Hkv, 32, 128] and v_cache [NB, Hkv, 128, 32] as for bf16, one OCP e4m3fn byte
     per element, and k_scale, v_scale fp32 [Hkv], contiguous, on the operands' device; a stored byte c of KV head g
-    stands for e4m3fn(c) * scale[g].  Every other operand rule of the two ops is unchanged; both caches have one
-    dtype; paged_prefill_attention does not read such a cache.  THE QUANTISATION RULE for an fp32 value z: a NaN
+    stands for e4m3fn(c) * scale[g].  Every other operand rule of the ops is unchanged; both caches have one
+    dtype; paged_decode_attention and paged_prefill_attention do not read such a cache.  THE QUANTISATION RULE for an fp32 value z: a NaN
     gives 0x7F | sign << 7; otherwise the magnitude is rounded to the nearest e4m3fn value, ties to even (the
     subnormal step is 2^-9 below 2^-6); whatever rounds above 448, +-Inf included, saturates to 0x7E; the sign bit
     is always carried (-0.0 and a negative value that rounds to zero give 0x80).  torch's cast does not saturate
@@ -818,11 +819,39 @@ def paged_prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     check=True verifies ctx_lens, the named block ids, q_start (non-decreasing within [0, Tq]),
     q_len <= ctx_lens and q_len <= max_q_len on the device first (one sync), and computes max_q_len
     when it is None.  check=False needs max_q_len and never syncs: for callers that guarantee all of
-    it, and under graph capture."""
-    name = "paged_prefill_attention"
-    _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, q_start, out)
+    it, and under graph capture.
+
+    The caches are bf16; paged_prefill_attention_kv8 is the same attention over an FP8 cache."""
+    return _paged_prefill("paged_prefill_attention", False, q, k_cache, v_cache, block_table, ctx_lens, q_start, None, None,
+                          max_q_len, out, scale, stream, check)
+
+
+def paged_prefill_attention_kv8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                                ctx_lens: torch.Tensor, q_start: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                                v_scale: Optional[torch.Tensor] = None, max_q_len: Optional[int] = None,
+                                out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                                stream: Optional[torch.cuda.Stream] = None, check: bool = True) -> torch.Tensor:
+    """paged_prefill_attention over an FP8 cache: both caches torch.float8_e4m3fn (FP8) with k_scale and v_scale, fp32
+    [Hkv], contiguous, on the operands' device (THE FP8 KV FORMAT, native/hip/api.h; rope_append writes it).  The
+    kernel dequantises in registers -- exactly -- and keeps the bf16 MFMAs: scores = mfma_sum * (scale * k_scale[g]),
+    the two scalars multiplied once in fp32, and out = bf16((acc / l) * v_scale[g]); q_len == 0, the rows outside
+    the chunks, max_q_len and check are paged_prefill_attention's.  check=True also verifies, in the same sync,
+    that the scales are finite and > 0.  bf16 caches (with or without scales) raise ValueError, mixed cache
+    dtypes TypeError.  (A function of its own, as paged_decode_attention_kv8 is: paged_prefill_attention's
+    parameter list is pinned.)"""
+    return _paged_prefill("paged_prefill_attention_kv8", True, q, k_cache, v_cache, block_table, ctx_lens, q_start, k_scale,
+                          v_scale, max_q_len, out, scale, stream, check)
+
+
+def _paged_prefill(name, fp8, q, k_cache, v_cache, block_table, ctx_lens, q_start, k_scale, v_scale, max_q_len, out, scale,
+                   stream, check):
+    """The two prefill wrappers: fp8 says which cache dtype the caller's function reads."""
+    _check_devices(name, q, k_cache, v_cache, block_table, ctx_lens, q_start, out, k_scale, v_scale)
     S, Hq, Hkv, NB, max_blocks, out, ld_q, ld_out, ld_table = _paged_attn_operands(
-        name, "token", q, k_cache, v_cache, block_table, ctx_lens, out, q_start)
+        name, "token", q, k_cache, v_cache, block_table, ctx_lens, out, q_start, kv8=fp8)
+    kv8 = _kv8_scales(name, k_cache, k_scale, v_scale, Hkv)
+    if fp8 and not kv8:
+        raise ValueError(f"{name} reads float8_e4m3fn caches, these are bf16: paged_prefill_attention reads them")
     Tq = q.shape[0]
     if max_q_len is None and not check:
         raise ValueError(f"{name}: check=False needs max_q_len")
@@ -840,7 +869,8 @@ def paged_prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
                 q_len = q_start[1:] - q_start[:-1]
                 bad = torch.stack([b.long() for b in _named_blocks_bad(block_table, ctx_lens, NB, max_blocks)]
                                   + [((q_len < 0).any() | (q_start[0] < 0) | (q_start[-1] > Tq)).long(),
-                                     (q_len > ctx_lens).any().long(), q_len.max().long()]).tolist()    # the one sync
+                                     (q_len > ctx_lens).any().long(), q_len.max().long()]
+                                  + ([_scales_bad(k_scale, v_scale).long()] if kv8 else [])).tolist()    # the one sync
             if bad[0]:
                 raise ValueError(f"{name}: a context length is outside [0, {ATTN_BLOCK_TOKENS * max_blocks}]")
             if bad[1]:
@@ -853,7 +883,13 @@ def paged_prefill_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
                 max_q_len = bad[4]
             elif bad[4] > max_q_len:
                 raise ValueError(f"{name}: a chunk of {bad[4]} tokens is longer than max_q_len = {max_q_len}")
-        if max_q_len:
+            if kv8 and bad[5]:
+                raise ValueError(f"{name}: k_scale and v_scale must be finite and > 0")
+        if max_q_len and kv8:
+            h.paged_prefill_kv8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                                v_scale.data_ptr(), block_table.data_ptr(), ctx_lens.data_ptr(), q_start.data_ptr(),
+                                out.data_ptr(), S, Hq, Hkv, int(max_q_len), ld_q, ld_out, ld_table, float(scale), sp)
+        elif max_q_len:
             h.paged_prefill_bf16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(),
                                  ctx_lens.data_ptr(), q_start.data_ptr(), out.data_ptr(), S, Hq, Hkv, int(max_q_len),
                                  ld_q, ld_out, ld_table, float(scale), sp)

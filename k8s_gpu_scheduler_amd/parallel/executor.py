@@ -156,16 +156,19 @@ def _kv8_scales(o: Op, device: torch.device) -> tuple:
             torch.full((o.rows,), KV8_V_SCALE, dtype=torch.float32, device=device))
 
 
-def _paged_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
-    """_paged_operands for decode over an FP8 cache, and (k_scale, v_scale): the caches repeat one seeded pattern
-    of finite e4m3fn codes of magnitude <= 2 (the low seven bits drawn from [0, 0x41): 0x40 is 2.0), any sign."""
+def _paged_kv8_operands(o: Op, g: torch.Generator, device: torch.device, q_rows: Optional[int] = None) -> tuple:
+    """_paged_operands over an FP8 cache, and (k_scale, v_scale): the caches repeat one seeded pattern of finite
+    e4m3fn codes of magnitude <= 2 (the low seven bits drawn from [0, 0x41): 0x40 is 2.0), any sign.  q_rows: the
+    rows of q and out (None: decode's o.M, one per sequence)."""
+    if q_rows is None:
+        q_rows = o.M
     T, D = loadgen.ATTN_BLOCK_TOKENS, loadgen.ATTN_HEAD_DIM
     if o.K % T:
         raise ValueError(f"attention context {o.K} is no multiple of {T}")
     per_seq = o.K // T
     nb = o.M * per_seq
     n = min(nb, ATTN_PATTERN_BLOCKS)
-    q = torch.randn(o.M, o.N, D, generator=g).to(torch.bfloat16).to(device)
+    q = torch.randn(q_rows, o.N, D, generator=g).to(torch.bfloat16).to(device)
 
     def cache(*shape: int) -> torch.Tensor:
         pat = torch.randint(0, 0x41, (n,) + shape, generator=g) | (torch.randint(0, 2, (n,) + shape, generator=g) << 7)
@@ -173,7 +176,7 @@ def _paged_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tupl
     kc, vc = cache(o.rows, T, D), cache(o.rows, D, T)
     table = torch.randperm(nb, generator=g).to(torch.int32).view(o.M, per_seq).to(device)
     ctx = torch.full((o.M,), o.K, dtype=torch.int32, device=device)
-    out = torch.empty(o.M, o.N, D, dtype=torch.bfloat16, device=device)
+    out = torch.empty(q_rows, o.N, D, dtype=torch.bfloat16, device=device)
     return (out, q, kc, vc, table, ctx) + _kv8_scales(o, device)
 
 
@@ -187,6 +190,15 @@ def _attn_split_kv8_operands(o: Op, g: torch.Generator, device: torch.device) ->
     ws = torch.empty(loadgen.decode_split_workspace_floats(o.M, o.N, o.splits), dtype=torch.float32, device=device)
     t = _paged_kv8_operands(o, g, device)
     return t[:6] + (ws,) + t[6:]
+
+
+def _prefill_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
+    """(out, q, k_cache, v_cache, table, ctx, q_start, k_scale, v_scale): the chunks as _prefill_operands packs them."""
+    if o.q > o.K:
+        raise ValueError(f"prefill chunk {o.q} is longer than the context {o.K}")
+    q_start = (torch.arange(o.M + 1, dtype=torch.int32) * o.q).to(device)
+    t = _paged_kv8_operands(o, g, device, o.M * o.q)
+    return t[:6] + (q_start,) + t[6:]
 
 
 def _rope_append_kv8_operands(o: Op, g: torch.Generator, device: torch.device) -> tuple:
@@ -365,6 +377,12 @@ def _launch_rope_append_kv8(o: Op, t: tuple, st, budget: int, blocks: int) -> No
                         k_scale=ks, v_scale=vs)
 
 
+def _launch_prefill_kv8(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
+    out, q, kc, vc, table, ctx, q_start, ks, vs = t
+    loadgen.paged_prefill_attention_kv8(q, kc, vc, table, ctx, q_start, ks, vs, max_q_len=o.q, out=out, stream=st,
+                                        check=False)
+
+
 def _launch_add_rmsnorm(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
     y, res_out, x, residual, weight = t
     loadgen.add_rmsnorm(x, weight, residual, out=y, residual_out=res_out, stream=st)
@@ -421,7 +439,8 @@ def _launch_triad(o: Op, t: tuple, st, budget: int, blocks: int) -> None:
 # temperature, top_k, top_p); moe_route (topk_ids, logits, topk_w, sorted_ids, tile_expert, expert_offsets,
 # slot_pos); moe_gemm (out, a, w, sorted_ids, tile_expert); moe_combine (out, y, slot_pos, topk_w); quant_mx (q, scales,
 # x); gemm_mx (c, a_q, a_scales, w_q, w_scales, bias); attn_kv8, attn_split_kv8 and rope_append_kv8 their bf16 kinds'
-# and (k_scale, v_scale), the caches float8_e4m3fn; triad (x, y, z), x = y + s z.
+# and (k_scale, v_scale), the caches float8_e4m3fn; prefill_kv8 prefill's and (k_scale, v_scale) likewise; triad
+# (x, y, z), x = y + s z.
 OP_KINDS = {
     "gemm": (_gemm_operands, _launch_gemm, 3),
     "gemm8": (_gemm_operands, _launch_gemm8, 3),
@@ -441,6 +460,7 @@ OP_KINDS = {
     "attn_kv8": (_attn_kv8_operands, _launch_attn_kv8, 0),
     "attn_split_kv8": (_attn_split_kv8_operands, _launch_attn_split_kv8, 0),
     "rope_append_kv8": (_rope_append_kv8_operands, _launch_rope_append_kv8, 0),
+    "prefill_kv8": (_prefill_kv8_operands, _launch_prefill_kv8, 0),
     "triad": (_triad_operands, _launch_triad, 0),
 }
 

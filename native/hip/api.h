@@ -181,6 +181,12 @@ void paged_decode_split_kv8(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, u
                             uintptr_t block_table, uintptr_t ctx_lens, uintptr_t workspace, uintptr_t out, int S,
                             int Hq, int Hkv, int kv_splits, int64_t ld_q, int64_t ld_out, int64_t ld_table,
                             float scale, uintptr_t stream);
+// paged_prefill_bf16 over such a cache -- native/hip/prefill_attn_kv8.hip: the same two scale rules, the division
+// before v_scale; workgroups are paged_prefill_workgroups'; S == 0 or max_q_len == 0 launches nothing
+void paged_prefill_kv8(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t k_scale, uintptr_t v_scale,
+                       uintptr_t block_table, uintptr_t ctx_lens, uintptr_t q_start, uintptr_t out, int S, int Hq,
+                       int Hkv, int max_q_len, int64_t ld_q, int64_t ld_out, int64_t ld_table, float scale,
+                       uintptr_t stream);
 // The launch knobs, each described once: name, min, max, default, kind.  Python gets set_<name> for every
 // row, knobs(), knob_defaults() and reset_knobs() (bindings.cpp); C++ reads knob(k_<name>).  An ON_OFF knob
 // takes any integer as on / off, a RANGE knob raises outside min..max.  What the values select is told where

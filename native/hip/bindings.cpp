@@ -142,6 +142,11 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("out"), py::arg("S"), py::arg("Hq"), py::arg("Hkv"), py::arg("kv_splits"), py::arg("ld_q"),
         py::arg("ld_out"), py::arg("ld_table"), py::arg("scale"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("paged_prefill_kv8", &gs::paged_prefill_kv8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("ctx_lens"), py::arg("q_start"),
+        py::arg("out"), py::arg("S"), py::arg("Hq"), py::arg("Hkv"), py::arg("max_q_len"), py::arg("ld_q"),
+        py::arg("ld_out"), py::arg("ld_table"), py::arg("scale"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
   m.def("gemm_mx_workgroups",&gs::gemm_mx_workgroups, py::arg("M"), py::arg("N"), py::arg("K"),
         py::arg("cu_budget") = 0);
   // the launch knobs (GS_KNOBS of api.h): set_<name>(value) for every row, and the whole table at once

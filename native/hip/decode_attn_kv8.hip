@@ -41,8 +41,6 @@
 namespace gs {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // 8 e4m3fn bytes (lo: elements 0 .. 3, hi: 4 .. 7, element j in bits 8 j of its word) as 8 bf16, exactly
@@ -59,15 +57,6 @@ __device__ __forceinline__ bf16x8 fp8x8_to_bf16(unsigned lo, unsigned hi) {
   r[6] = (__bf16)d[0];
   r[7] = (__bf16)d[1];
   return r;
-}
-
-// the 4 K pieces of one (block, KV head) slab: tile t, half h is d = 64 h + 16 g .. + 15 of the lane's token
-// 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
-__device__ __forceinline__ void load_k8(u32x4 (&kf)[2][2], const uint8_t* p) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) kf[t][h] = *reinterpret_cast<const u32x4*>(p + t * 4 * kHeadDim + h * 64);
 }
 
 // walk_blocks of decode_attn.hip over byte caches; sscale = scale * k_scale[kvh]

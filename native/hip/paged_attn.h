@@ -26,6 +26,19 @@ __device__ __forceinline__ void load_k(bf16x8 (&kf)[2][4], const __bf16* p) {
       kf[t][kk] = *reinterpret_cast<const bf16x8*>(p + t * 4 * kHeadDim + kk * 32);
 }
 
+// What the readers of an FP8 cache (decode_attn_kv8.hip, prefill_attn_kv8.hip) share: the byte fragments
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// the 4 K pieces of one (block, KV head) slab: tile t, half h is d = 64 h + 16 g .. + 15 of the lane's token
+// 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
+__device__ __forceinline__ void load_k8(u32x4 (&kf)[2][2], const uint8_t* p) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) kf[t][h] = *reinterpret_cast<const u32x4*>(p + t * 4 * kHeadDim + h * 64);
+}
+
 // What the decode kernels (decode_attn.hip over a bf16 cache, decode_attn_kv8.hip over an FP8 one) share beyond
 // that: the per-wave partials in LDS, their merge and the final division.
 constexpr int kWaves = 4;
