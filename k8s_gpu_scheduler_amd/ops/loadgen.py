@@ -2,7 +2,7 @@
 headers, native/hip/triad.hip, native/hip/gather.hip, native/hip/decode_attn.hip,
 native/hip/prefill_attn.hip, native/hip/rope_append.hip, native/hip/rmsnorm.hip, native/hip/swiglu.hip,
 native/hip/sample.hip, native/hip/moe_route.hip, native/hip/moe_gemm.hip, native/hip/moe_combine.hip,
-native/hip/rope_append_kv8.hip, native/hip/decode_attn_kv8.hip, native/hip/prefill_attn_kv8.hip).
+native/hip/decode_attn_kv8.hip, native/hip/prefill_attn_kv8.hip; rope_append.hip writes FP8 caches as well).
 
 `gemm(a, bt)` computes act(a @ bt.T + bias) in bf16 on MFMA, `gemm_fp8` the same with OCP
 e4m3fn operands on the block-scaled fp8 MFMA; `triad(a, b, c, s)` streams HBM;

@@ -157,7 +157,7 @@ void gemm_mx_nt(uintptr_t a, uintptr_t a_scales, uintptr_t w, uintptr_t w_scales
 int gemm_mx_workgroups(int M, int N, int K, int cu_budget);
 // the fill rule of gemm_fp8_nt and gemm_mx_nt (gemm.hip): 128 x 128 tiles, else 64 x 64
 bool fp8_tile_128(int M, int N, int cu_budget);
-// FP8 paged-KV cache -- native/hip/rope_append_kv8.hip, decode_attn_kv8.hip.  THE FP8 KV FORMAT: k_cache uint8
+// FP8 paged-KV cache -- native/hip/rope_append.hip, decode_attn_kv8.hip.  THE FP8 KV FORMAT: k_cache uint8
 // [NB, Hkv, 32, 128] and v_cache uint8 [NB, Hkv, 128, 32], the logical layout of the bf16 caches with one OCP e4m3fn
 // byte per element; k_scale and v_scale fp32 [Hkv] (4-byte aligned).  A stored byte c of KV head g stands for
 // e4m3fn(c) * scale[g].  THE QUANTISATION RULE for an fp32 value z (the writer computes z = value / scale[g], an IEEE

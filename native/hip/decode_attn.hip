@@ -109,7 +109,7 @@ __device__ __forceinline__ void walk_blocks(Partials& sm, const __bf16* __restri
     // unconditional and reads an entry that names a block
     int next_id = trow[min(b + kWaves, last)];
     bf16x8 kf[2][4];
-    load_k(kf, klane + slab);
+    KvBf16::load_k(kf, klane + slab);
     // one block.  more: another block of this wave follows -- its K and the id of the one after
     // are loaded behind this block's V, and it is a full block (only the sequence's last block,
     // which is its wave's last, can have slots past ctx); the two cases are separate code, so
@@ -123,7 +123,7 @@ __device__ __forceinline__ void walk_blocks(Partials& sm, const __bf16* __restri
       bf16x8 kn[2][4];
       if constexpr (more) {
         slab = ((size_t)next_id * Hkv + kvh) * kSlab;
-        load_k(kn, klane + slab);
+        KvBf16::load_k(kn, klane + slab);
         next_id = trow[min(b + 2 * kWaves, last)];
       }
       // S^T = K . Q^T

@@ -98,7 +98,7 @@ __device__ __forceinline__ void walk_blocks_kv8(Partials& sm, const __bf16* __re
     size_t slab = ((size_t)trow[b] * Hkv + kvh) * kSlab;
     int next_id = trow[min(b + kWaves, last)];
     u32x4 kf[2][2];
-    load_k8(kf, klane + slab);
+    KvFp8::load_k(kf, klane + slab);
     auto step = [&](auto more_c) {
       constexpr bool more = decltype(more_c)::value;
       u32x2 vb[8];
@@ -108,7 +108,7 @@ __device__ __forceinline__ void walk_blocks_kv8(Partials& sm, const __bf16* __re
       u32x4 kn[2][2];
       if constexpr (more) {
         slab = ((size_t)next_id * Hkv + kvh) * kSlab;
-        load_k8(kn, klane + slab);
+        KvFp8::load_k(kn, klane + slab);
         next_id = trow[min(b + 2 * kWaves, last)];
       }
       // S^T = K . Q^T
@@ -238,11 +238,6 @@ __global__ void __launch_bounds__(256) paged_decode_merge_kv8_kernel(const float
   const int s = row / Hq, h = row % Hq;
   *reinterpret_cast<bf16x8*>(out + (size_t)s * ld_out + (size_t)h * kHeadDim + d0) =
       normalised(acc, lsum, v_scale[h / group]);
-}
-
-void check_scales(const char* name, uintptr_t k_scale, uintptr_t v_scale) {
-  if (!k_scale || !v_scale) throw std::runtime_error(std::string(name) + ": k_scale and v_scale are needed");
-  if (k_scale % 4 || v_scale % 4) throw std::runtime_error(std::string(name) + ": k_scale / v_scale must be 4-byte aligned");
 }
 
 }  // namespace

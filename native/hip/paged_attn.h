@@ -1,5 +1,6 @@
-// What the two paged-KV attention kernels (decode_attn.hip, prefill_attn.hip) share: the fixed sizes of
-// the cache layout, the MFMA fragment types and the host-side operand checks of their launch functions.
+// What the paged-KV kernels (decode_attn.hip, decode_attn_kv8.hip, prefill_attn.hip, prefill_attn_kv8.hip,
+// rope_append.hip) share: the fixed sizes of the cache layout, the MFMA fragment types, the two cache formats
+// (bf16 and FP8) and the host-side operand checks of their launch functions.
 #pragma once
 #include <string>
 
@@ -10,37 +11,69 @@ namespace gs {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x8_bits __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kHeadDim = 128;
 constexpr int kBlockTokens = 32;
 constexpr int kMaxGroup = 16;                     // the MFMA's column dimension
 constexpr float kLog2e = 1.44269504088896340736f;
 
-// the 8 K fragments of one (block, KV head) slab: tile t, k-step kk is d = 32 kk + 8 g .. + 7 of
-// the lane's token 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
-__device__ __forceinline__ void load_k(bf16x8 (&kf)[2][4], const __bf16* p) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-      kf[t][kk] = *reinterpret_cast<const bf16x8*>(p + t * 4 * kHeadDim + kk * 32);
-}
+// The two cache formats, described once for the kernels that walk a cache (decode_attn.hip, decode_attn_kv8.hip,
+// the two prefill kernels) or write one (rope_append.hip): the element type, the register images of a block's K
+// and of one V fragment, where the lane's d starts in a row, which d the k-step kk of the S^T MFMAs multiplies,
+// how a block's K is loaded, and whether the format has scales.  The byte -> bf16 conversion in front of an MFMA
+// is NOT here: decode and prefill use different instructions on purpose, each file has its own.  Nor is the mask of
+// the slots past ctx in a sequence's last block (for FP8 the byte AND with keep / mlo / mhi): it deliberately stays
+// in each kernel's own loop, because as a function of the format the compiler's code for paged_prefill_kv8_kernel
+// changed, and the decode walks are kept as they were (profiles/r19_kv_format).
 
-// What the readers of an FP8 cache (decode_attn_kv8.hip, prefill_attn_kv8.hip) share: the byte fragments
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// bf16: k_cache [NB, Hkv, 32, 128] and v_cache [NB, Hkv, 128, 32] of __bf16.  The lane holds d = 32 kk + 8 g
+// .. + 7 of its token for k-step kk (8 loads of 16 bytes per block and lane) and, per V fragment, the tokens
+// 8 g .. 8 g + 7 of one d (8 loads of 16 bytes)
+struct KvBf16 {
+  typedef __bf16 Elem;
+  typedef bf16x8 KBlock[2][4];                    // [tile t][k-step kk]
+  typedef bf16x8 VFrag;
+  static constexpr bool kScales = false;
+  static constexpr int kLaneD = 8;                // the lane's first d in a row is kLaneD * g
+  static __device__ __forceinline__ int q_offset(int kk) { return 32 * kk; }
 
-// the 4 K pieces of one (block, KV head) slab: tile t, half h is d = 64 h + 16 g .. + 15 of the lane's token
-// 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
-__device__ __forceinline__ void load_k8(u32x4 (&kf)[2][2], const uint8_t* p) {
+  // the 8 K fragments of one (block, KV head) slab: tile t, k-step kk is d = 32 kk + 8 g .. + 7 of
+  // the lane's token 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
+  static __device__ __forceinline__ void load_k(KBlock& kf, const __bf16* p) {
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int h = 0; h < 2; ++h) kf[t][h] = *reinterpret_cast<const u32x4*>(p + t * 4 * kHeadDim + h * 64);
-}
+      for (int kk = 0; kk < 4; ++kk) kf[t][kk] = *reinterpret_cast<const bf16x8*>(p + t * 4 * kHeadDim + kk * 32);
+  }
+};
 
-// What the decode kernels (decode_attn.hip over a bf16 cache, decode_attn_kv8.hip over an FP8 one) share beyond
-// that: the per-wave partials in LDS, their merge and the final division.
+// FP8 (THE FP8 KV FORMAT, api.h): the same two layouts of OCP e4m3fn bytes, one fp32 scale per KV head.  A K row is
+// 128 bytes: the lane loads the two 16-byte pieces d = 64 h + 16 g .. + 15 of its token, and k-step kk = 2 h + e
+// takes bytes 8 e .. 8 e + 7 of piece h -- a permutation of bf16's d map under which the Q^T fragments are loaded
+// too (q_offset), so every (q[d], K[d]) pair still meets once (decode_attn_kv8.hip's header has the argument).
+// A V fragment is 8 bytes
+struct KvFp8 {
+  typedef uint8_t Elem;
+  typedef u32x4 KBlock[2][2];                     // [tile t][piece h]: k-steps 2 h and 2 h + 1
+  typedef u32x2 VFrag;
+  static constexpr bool kScales = true;
+  static constexpr int kLaneD = 16;
+  static __device__ __forceinline__ int q_offset(int kk) { return 64 * (kk >> 1) + 8 * (kk & 1); }
+
+  // the 4 K pieces of one (block, KV head) slab: tile t, piece h is d = 64 h + 16 g .. + 15 of the lane's token
+  // 8 (rho >> 2) + 4 t + (rho & 3) -- p already points at the lane's place
+  static __device__ __forceinline__ void load_k(KBlock& kf, const uint8_t* p) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) kf[t][h] = *reinterpret_cast<const u32x4*>(p + t * 4 * kHeadDim + h * 64);
+  }
+};
+
+// What only the decode kernels (decode_attn.hip over a bf16 cache, decode_attn_kv8.hip over an FP8 one) share:
+// the per-wave partials in LDS, their merge and the final division.
 constexpr int kWaves = 4;
 constexpr int kOLd = kHeadDim + 4;                // fp32 row of the LDS image: 528 bytes, 16-byte aligned
 constexpr int kPartLd = kOLd;                     // a split's workspace row: 128 accumulators, m, l, 2 words unused
@@ -169,6 +202,12 @@ inline void check_paged_operands(const std::string& name, const char* rows, uint
   if (q % 16 || out % 16 || k_cache % 16 || v_cache % 16)
     throw std::runtime_error(name + ": q / out / k_cache / v_cache must be 16-byte aligned");
   if (block_table % 4 || ctx_lens % 4) throw std::runtime_error(name + ": block_table / ctx_lens must be 4-byte aligned");
+}
+
+// The throws of every launch function over an FP8 cache: the two per-KV-head scale vectors
+inline void check_scales(const std::string& name, uintptr_t k_scale, uintptr_t v_scale) {
+  if (!k_scale || !v_scale) throw std::runtime_error(name + ": k_scale and v_scale are needed");
+  if (k_scale % 4 || v_scale % 4) throw std::runtime_error(name + ": k_scale / v_scale must be 4-byte aligned");
 }
 
 }  // namespace gs

@@ -96,9 +96,9 @@ __global__ void __launch_bounds__(256, 2) paged_prefill_attn_kernel(
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) qf[j][kk] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     if (have[j]) {
-      const __bf16* qp = q + (size_t)(row0 + i) * ld_q + (size_t)(kvh * group + h) * kHeadDim + 8 * g;
+      const __bf16* qp = q + (size_t)(row0 + i) * ld_q + (size_t)(kvh * group + h) * kHeadDim + KvBf16::kLaneD * g;
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) qf[j][kk] = *reinterpret_cast<const bf16x8*>(qp + kk * 32);
+      for (int kk = 0; kk < 4; ++kk) qf[j][kk] = *reinterpret_cast<const bf16x8*>(qp + KvBf16::q_offset(kk));
     }
   }
 
@@ -115,13 +115,13 @@ __global__ void __launch_bounds__(256, 2) paged_prefill_attn_kernel(
   const int* trow = block_table + (size_t)s * ld_table;
   constexpr size_t kSlab = (size_t)kBlockTokens * kHeadDim;                // one (block, KV head) of K or V
   // the lane's place in a slab
-  const __bf16* klane = k_cache + (size_t)(8 * (col >> 2) + (col & 3)) * kHeadDim + 8 * g;
+  const __bf16* klane = k_cache + (size_t)(8 * (col >> 2) + (col & 3)) * kHeadDim + KvBf16::kLaneD * g;
   const __bf16* vlane = v_cache + (size_t)col * kBlockTokens + 8 * g;
   int b = 0;
   size_t slab = ((size_t)trow[0] * Hkv + kvh) * kSlab;
   int next_id = trow[min(1, last)];
-  bf16x8 kf[2][4];
-  load_k(kf, klane + slab);
+  KvBf16::KBlock kf;
+  KvBf16::load_k(kf, klane + slab);
 
   // One loop with wave-uniform branches around the mask code: as two loops, a mask-free one and a
   // masked one, the register state carried from one into the other cost 19 to 34 spilled VGPRs.
@@ -144,13 +144,12 @@ __global__ void __launch_bounds__(256, 2) paged_prefill_attn_kernel(
       }
     __builtin_amdgcn_sched_barrier(0);
     slab = ((size_t)next_id * Hkv + kvh) * kSlab;
-    load_k(kf, klane + slab);
+    KvBf16::load_k(kf, klane + slab);
     next_id = trow[min(b + 2, last)];
     __builtin_amdgcn_sched_barrier(0);
     const int tok0 = b * kBlockTokens + 8 * g;       // this lane's first token
     if (masked && (b + 1) * kBlockTokens > ctx) {    // the sequence's last block, not full
       // a 32-bit word of a V fragment holds tokens tok0 + 2 w and tok0 + 2 w + 1
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
       u32x4 keep;
 #pragma unroll
       for (int w = 0; w < 4; ++w)

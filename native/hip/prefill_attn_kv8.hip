@@ -93,9 +93,9 @@ __global__ void __launch_bounds__(256, 2) paged_prefill_kv8_kernel(
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) qf[j][kk] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     if (have[j]) {
-      const __bf16* qp = q + (size_t)(row0 + i) * ld_q + (size_t)(kvh * group + h) * kHeadDim + 16 * g;
+      const __bf16* qp = q + (size_t)(row0 + i) * ld_q + (size_t)(kvh * group + h) * kHeadDim + KvFp8::kLaneD * g;
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) qf[j][kk] = *reinterpret_cast<const bf16x8*>(qp + (kk >> 1) * 64 + (kk & 1) * 8);
+      for (int kk = 0; kk < 4; ++kk) qf[j][kk] = *reinterpret_cast<const bf16x8*>(qp + KvFp8::q_offset(kk));
     }
   }
 
@@ -112,18 +112,18 @@ __global__ void __launch_bounds__(256, 2) paged_prefill_kv8_kernel(
   const int* trow = block_table + (size_t)s * ld_table;
   constexpr size_t kSlab = (size_t)kBlockTokens * kHeadDim;                // bytes of one (block, KV head) of K or V
   // the lane's place in a slab
-  const uint8_t* klane = k_cache + (size_t)(8 * (col >> 2) + (col & 3)) * kHeadDim + 16 * g;
+  const uint8_t* klane = k_cache + (size_t)(8 * (col >> 2) + (col & 3)) * kHeadDim + KvFp8::kLaneD * g;
   const uint8_t* vlane = v_cache + (size_t)col * kBlockTokens + 8 * g;
   int b = 0;
   size_t slab = ((size_t)trow[0] * Hkv + kvh) * kSlab;
   int next_id = trow[min(1, last)];
-  u32x4 kf[2][2];
-  load_k8(kf, klane + slab);
+  KvFp8::KBlock kf;
+  KvFp8::load_k(kf, klane + slab);
 
   // One loop with wave-uniform branches around the mask code, as in prefill_attn.hip
   for (; b <= last; ++b) {
     const bool masked = b >= nfull;                  // some token of the block lies above some column's position (or past ctx)
-    u32x2 vb[8];
+    KvFp8::VFrag vb[8];
 #pragma unroll
     for (int db = 0; db < 8; ++db)
       vb[db] = *reinterpret_cast<const u32x2*>(vlane + slab + (size_t)db * 16 * kBlockTokens);
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256, 2) paged_prefill_kv8_kernel(
       }
     __builtin_amdgcn_sched_barrier(0);
     slab = ((size_t)next_id * Hkv + kvh) * kSlab;
-    load_k8(kf, klane + slab);
+    KvFp8::load_k(kf, klane + slab);
     next_id = trow[min(b + 2, last)];
     __builtin_amdgcn_sched_barrier(0);
     const int tok0 = b * kBlockTokens + 8 * g;       // this lane's first token
@@ -230,8 +230,7 @@ void paged_prefill_kv8(uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintpt
                        ld_out, ld_table);
   if (max_q_len < 0) throw std::runtime_error("paged_prefill_kv8: negative max_q_len");
   if (q_start % 4) throw std::runtime_error("paged_prefill_kv8: q_start must be 4-byte aligned");
-  if (!k_scale || !v_scale) throw std::runtime_error("paged_prefill_kv8: k_scale and v_scale are needed");
-  if (k_scale % 4 || v_scale % 4) throw std::runtime_error("paged_prefill_kv8: k_scale / v_scale must be 4-byte aligned");
+  check_scales("paged_prefill_kv8", k_scale, v_scale);
   const int grid = paged_prefill_workgroups(S, Hq, Hkv, max_q_len);
   if (grid == 0) return;
   hipLaunchKernelGGL(paged_prefill_kv8_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),

@@ -1,5 +1,5 @@
 """Time per launch of the FP8 paged-KV kernels on the MI355X beside their bf16 siblings -- decode attention, split-KV
-decode attention and rope_append over float8_e4m3fn caches (native/hip/decode_attn_kv8.hip, rope_append_kv8.hip)
+decode attention and rope_append over float8_e4m3fn caches (native/hip/decode_attn_kv8.hip, rope_append.hip)
 against the same shapes over bf16 caches -- and the stream triad over a working set of 1 GiB, all in one process.
 
 Shapes: the llm_decode_256 attention (256 sequences x 1,024 tokens, 32 query heads over 8 KV heads), the same at 4,096
